@@ -13,16 +13,23 @@ metric is quoted on (BASELINE configs[1]: FFHQ-256 architecture, batch 4 per GPU
 random-init (torch.manual_seed(1); the FFHQ checkpoint is a download), reals are seeded U(-1,1)
 batches already resident in HBM.  value = global batch * K / max-over-ranks wall time.
 
-Extra objects on the JSON line:
+A plain run sets up, warms up, times the K steps and prints the line.  --dump-outputs DIR writes what the last timed step
+left for its caller as DIR/<name>.npy (float32): the step losses and scores, the path-length mean and a fixed seeded
+sample of each network's parameters (G, D and their EMA copies).  Inputs are seeded, so two builds can be compared file
+by file.
+
+With --full, extra objects on the JSON line, all measured after the timed steps:
   roofline      the dominant kernel (conv_igemm_kernel, fp16x3 MFMA): algorithmic FLOPs / time,
                 timed per launch with HIP events on the launch stream in an instrumented repeat of
                 the same steps (the timed region itself carries no events)
   cpu_baseline  the CPU oracle (port of the reference's CPU formulation) timed on this box's host
                 cores on a bounded sample (rank 0, N = 1 only)
+  step_ms, nonreg_iteration, amortised16, fisher_sweep, fisher_sweep_64, eval_sampling, dp1_forced
 """
 import argparse
 import json
 import os
+import random
 import sys
 import time
 
@@ -33,6 +40,23 @@ sys.path.insert(0, ROOT)
 
 MFMA_BF16_DENSE_PEAK_TFLOPS = 2500.0      # /opt/skills/guides/MI355X_MICROARCH.md
 HBM_LARGE_BYTES = 16 << 20
+DUMP_SAMPLE = 1 << 21                      # parameters sampled per network by --dump-outputs: 4 x 8 MiB
+
+
+def dump_outputs(path, tr):
+    """The arrays a caller of the timed loop gets after its last step, as float32 .npy files in `path`: every entry of the
+    trainer's `losses` (latest D, R1, G and path-length step), the path-length mean, and DUMP_SAMPLE parameter values of each
+    network drawn at fixed seeded positions of its flat buffer (the whole buffers are ~470 MB)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    torch.cuda.synchronize()
+    arrays = {f'loss_{k}': v for k, v in tr.losses.items()}
+    arrays['mean_path_length'] = tr.mean_path_length
+    for name, fp in (('g', tr.g_flat), ('d', tr.d_flat), ('g_ema', tr.g_ema_flat), ('d_ema', tr.d_ema_flat)):
+        idx = np.sort(np.random.default_rng(0).choice(fp.total, min(fp.total, DUMP_SAMPLE), replace=False))
+        arrays[f'{name}_params'] = fp.flat[torch.from_numpy(idx).to(fp.flat.device)]
+    for name, v in arrays.items():
+        np.save(os.path.join(path, name + '.npy'), torch.as_tensor(v).detach().float().cpu().numpy())
 
 
 def cpu_baseline(size=256, batch=2, timed=2):
@@ -158,6 +182,10 @@ def main():
     ap.add_argument('--eval', action='store_true', help='(default on) also time G inference (BASELINE config 4: batches of 25)')
     ap.add_argument('--no-extras', action='store_true', help='skip the untimed extras: 64-sample Fisher sweep (config 5), G inference (config 4)')
     ap.add_argument('--fisher-img', type=int, default=2, help='samples of the (untimed) Fisher sweep that sets the masks')
+    ap.add_argument('--full', action='store_true', help='after the headline also measure the extras: Fisher sweep time, '
+                    'per-step-type times, roofline, 64-sample sweep, G inference, dp1_forced, CPU baseline (the --no-* '
+                    'switches and --eval select among them)')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='write what the last timed step computed to DIR/<name>.npy')
     args = ap.parse_args()
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         sys.exit(self_launch(args.gpus))
@@ -216,6 +244,7 @@ def main():
         dp.broadcast_params([g, d, g_ema, d_ema])
     tr = RickTrainer(cfg, g, d, g_ema, d_ema, dp=dp)
     torch.manual_seed(1234 + rank)                         # per-rank latents / noise
+    random.seed(1234 + rank)                               # host-side style-mixing draws: same inputs in every run
 
     reals = [synth_reals(cfg.batch, cfg.size, seed=100 * rank + j).to(dev) for j in range(4)]
     # steady state: a Fisher sweep has run, masks are active (untimed; it recurs every fisher_freq iterations)
@@ -234,17 +263,6 @@ def main():
             print(f'[bench] hipGraph capture failed ({type(e).__name__}: {e}); issuing launches eagerly', file=sys.stderr)
             use_graphs = False
             tr.enable_graphs(False)
-
-    fisher_ms = None
-    if not args.no_fisher and use_graphs:
-        # the sweep itself (untimed in `value`: it recurs every fisher_freq = 50 iterations): once more to capture its
-        # per-sample graph, then timed.  Every rank runs it (its per-filter all-reduce must stay matched).
-        tr.fisher_sweep(*fisher_in, first=True)
-        torch.cuda.synchronize()
-        tf = time.perf_counter()
-        tr.fisher_sweep(*fisher_in, first=True)
-        torch.cuda.synchronize()
-        fisher_ms = 1e3 * (time.perf_counter() - tf)
 
     def run(n, start):
         for k in range(n):
@@ -284,9 +302,18 @@ def main():
                   'rccl_ranks': world if world > 1 and dist.get_backend() == 'nccl' else (0 if world > 1 else None),
                   'ms_per_step_per_rank': rank_ms},
     }
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, tr)
 
-    if fisher_ms is not None:
-        out['fisher_sweep'] = {'ms': fisher_ms, 'samples_this_rank': len(mine), 'samples': cfg.num_fisher_img,
+    if args.full and not args.no_fisher and use_graphs:
+        # the sweep itself (untimed in `value`: it recurs every fisher_freq = 50 iterations): once more to capture its
+        # per-sample graph, then timed.  Every rank runs it (its per-filter all-reduce must stay matched).
+        tr.fisher_sweep(*fisher_in, first=True)
+        torch.cuda.synchronize()
+        tf = time.perf_counter()
+        tr.fisher_sweep(*fisher_in, first=True)
+        torch.cuda.synchronize()
+        out['fisher_sweep'] = {'ms': 1e3 * (time.perf_counter() - tf), 'samples_this_rank': len(mine), 'samples': cfg.num_fisher_img,
                                'note': 'whole sweep (per-sample G/D forward + both gradients at batch 1 replayed from a captured '
                                        'graph, grad^2 accumulate, per-filter reduce, percentile decisions, mask upload); not part '
                                        'of `value`; the README recipe runs 5 samples every 50 iterations'}
@@ -294,7 +321,7 @@ def main():
     # ---- per-step-type times (untimed extra pass, every rank runs it so collectives stay matched): HIP events on the
     # launch stream after every step of 32 more iterations = two full R1 periods (8 path-length steps, 2 R1 steps, 24 iterations
     # without a regulariser: SURVEY 8d's headline is the median of >= 20 of those)
-    if not args.no_step_times:
+    if args.full and not args.no_step_times:
         tr.step_events = []
         run(32, i0 + args.warmup + args.steps)
         torch.cuda.synchronize()
@@ -323,7 +350,7 @@ def main():
         out['amortised16'] = {'ms_per_iteration': tot16 / len(iters), 'images_per_s': cfg.batch * world * len(iters) / (1e-3 * tot16),
                               'note': f'{len(iters)} consecutive iterations; per 16: 16 D + 16 G + 1 R1 + 4 path-length steps'}
 
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         # instrumented repeat of 16 iterations: HIP events around every conv-family launch (eager issue; every rank
         # runs it — the bucketed all-reduces must stay matched — rank 0 reports)
         tr.enable_graphs(False)
@@ -422,7 +449,7 @@ def main():
             for name, (by, dt, n, lby, ldt, ln) in sorted(hbm.items(), key=lambda kv_: -kv_[1][1])]
         conv_s = sum(a[1] for a in agg.values()) / 16
         out['roofline']['conv_family_ms_per_step'] = 1e3 * conv_s
-    if rank == 0 and not args.no_extras:
+    if rank == 0 and args.full and not args.no_extras:
         # BASELINE config 5 at its own size: a 64-sample Fisher sweep (10 shipped-latent stand-ins + 54 seeded), this rank's
         # share, from the captured per-sample graph
         from rick_amd.synth import synth_latents as _sl, synth_reals as _sr
@@ -441,7 +468,7 @@ def main():
                                       'note': 'BASELINE config 5 (num_fisher_img = 64) on one GPU: per-sample graph replay, grad^2 '
                                               'accumulate, per-filter reduce, decisions, mask upload'}
         cfg.num_fisher_img = cfg64
-    if rank == 0 and (args.eval or not args.no_extras):
+    if rank == 0 and args.full and (args.eval or not args.no_extras):
         from rick_amd.evaluate import sample_images
         n = 500
         sample_images(g_ema, 50, 25)
@@ -451,7 +478,7 @@ def main():
         torch.cuda.synchronize()
         out['eval_sampling'] = {'images_per_s': n / (time.perf_counter() - t0), 'batch': 25, 'images': n,
                                 'note': 'g_ema inference loop of gan_training/eval.py:34-41, images kept on device'}
-    if rank == 0 and world == 1 and not args.no_extras and use_graphs:
+    if rank == 0 and world == 1 and args.full and not args.no_extras and use_graphs:
         # The data-parallel code path on ONE GPU: the same loop through DataParallelGrads(force=True) on a single-rank RCCL
         # ('nccl') group — forward/backward graph, ncclAvg per 32 MiB bucket on RCCL's stream, optimiser graph deferred behind
         # the next step's head.  With one rank the exchange is the identity, so the ratio to the plain loop is the pipeline's
@@ -497,7 +524,7 @@ def main():
             dist.destroy_process_group()
         except Exception as e:                             # noqa: BLE001 — an extra must not cost the measurement
             out['dp1_forced'] = {'error': f'{type(e).__name__}: {e}'}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         out['cpu_baseline'] = cpu_baseline(cfg.size)
     if rank == 0:
         emit(out)

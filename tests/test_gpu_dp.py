@@ -287,7 +287,7 @@ def test_bench_self_launch_two_ranks_one_gpu():
     env.pop('WORLD_SIZE', None)
     env.pop('RANK', None)
     r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--size', '32', '--batch', '2',
-                        '--steps', '4', '--warmup', '2', '--no-cpu-baseline', '--fisher-img', '2'],
+                        '--steps', '4', '--warmup', '2', '--full', '--no-cpu-baseline', '--fisher-img', '2'],
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{')]

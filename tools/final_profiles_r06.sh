@@ -11,7 +11,7 @@ rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $o/pmc_write -o
 python3 tools/pmc_traffic.py $o/pmc_fetch $o/pmc_write $o/r06_pmc_traffic.json > $o/pmc_traffic.txt 2>&1
 rm -rf $o/pmc_fetch $o/pmc_write
 cp $o/r06_pmc_traffic.json profiles/r06_pmc_traffic.json      # (bench.py reads the newest committed counter file: the line below carries these)
-python3 bench.py > $o/bench_line.json 2> $o/bench_stderr.log
+python3 bench.py --full > $o/bench_line.json 2> $o/bench_stderr.log
 for spec in "conv 512 512 64 8" "conv_split 512 512 64 8" "conv 128 128 256 8" "conv_split 128 128 256 8" "wgrad 512 512 64 8" "wgrad_split 512 512 64 8" "wgrad_s2 256 512 64 8" "wgrad_s2_split 256 512 64 8" "conv_s2 256 512 64 8" "conv_s2_split 256 512 64 8" "convT2 512 256 64 8" "convT2_split 512 256 64 8"; do
   tag=$(echo $spec | tr ' ' '_')
   bash tools/pmc_run.sh $o/k_$tag $spec > $o/k_$tag.txt 2>&1
