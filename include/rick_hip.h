@@ -532,6 +532,33 @@ int rick_image_batch_f32(const uint8_t *images, const int64_t *index, const uint
 /* PNG scanline reconstruction (filter types 0-4), in place, HOST memory: H rows of 1 filter byte + stride bytes. */
 int rick_png_unfilter(uint8_t *data, int H, int stride, int bpp);
 
+/* ---------------------------------------------------------------------------------------
+ * Adaptive discriminator augmentation — replaces augment(img, p, (G, C)) of non_leaking.py:316-398 (random_apply_affine:
+ * reflect pad -> upfirdn2d(up=2) -> grid_sample -> upfirdn2d(down=2) -> crop; random_apply_color) for given matrices.
+ * Images are planar fp32 [N, 3, H, W], contiguous (the generator's output, the rick_image_batch_f32 batch, the
+ * discriminator's input).  Per-sample parameters live in device memory (`params`, N entries), so a captured graph replays
+ * with new transforms after one copy into the block:
+ *   a     maps warped-region pixel (c, r) to up-sampled canvas coordinates: ix = a0 c + a1 r + a2, iy = a3 c + a4 r + a5
+ *         (the region is warped-canvas rows 2 py1 .. 2 py1 + 2H + 9, columns 2 px1 .. 2 px1 + 2W + 9);
+ *   ainv  the inverse of the 2x2 part (c = ainv0 ex + ainv1 ey, r = ainv2 ex + ainv3 ey for ex = ix - a2, ey = iy - a5);
+ *   col   the first three rows of the 4x4 colour matrix, row-major;
+ *   py1, px1  the sample's low reflect pads (without the 6 of the FIR), hp, wp its padded-canvas size
+ *         (H + py1 + py2 + 12, W + px1 + px2 + 12); the up-sampled canvas is (2 hp - 11) x (2 wp - 11).
+ * Pads must satisfy pad + 6 < H (resp. W), as the reference's reflect pad requires.
+ * rick_augment_fwd_f32: out = augment(x) (bias != 0: with the colour offset col[:, 3]; 0: the linear part only);
+ * rick_augment_adj_f32: gx = the transpose of the linear part applied to gy.  Both use `ws`, rick_augment_workspace_floats()
+ * floats, and write every element of their output (no accumulation, no atomics: bit-identical from run to run). */
+typedef struct {
+    double a[6];
+    double ainv[4];
+    float col[12];
+    int py1, px1, hp, wp;
+} rick_aug_param;
+int64_t rick_augment_workspace_floats(int N, int H, int W);
+int rick_augment_fwd_f32(const float *x, const rick_aug_param *params, float *ws, float *out, int N, int H, int W, int bias,
+                         void *stream);
+int rick_augment_adj_f32(const float *gy, const rick_aug_param *params, float *ws, float *gx, int N, int H, int W, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

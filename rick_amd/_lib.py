@@ -156,6 +156,9 @@ SIGNATURES = {
     'rick_ema_f32': (c_int, [c_fp, c_fp, c_i64, c_f, c_fp]),
     'rick_image_batch_f32': (c_int, [c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, c_fp]),
     'rick_png_unfilter': (c_int, [c_fp, c_int, c_int, c_int]),
+    'rick_augment_workspace_floats': (c_i64, [c_int, c_int, c_int]),
+    'rick_augment_fwd_f32': (c_int, [c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, c_fp]),
+    'rick_augment_adj_f32': (c_int, [c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_fp]),
 }
 
 if not os.path.exists(LIB_PATH):

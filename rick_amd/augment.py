@@ -8,11 +8,18 @@ followed by a random 4x4 colour transform.  The two FIR passes run on the generi
 on the device.  The transform matrices are sampled on the host exactly like the reference does (same
 distributions, same draw order from torch's CPU generator, so a seed reproduces the reference's G / C);
 they can also be passed in, which is how the parity tests pin the image path to the reference.
+
+CUDA float32 images take the fused path: four static-shape HIP kernels (rick_amd/csrc/augment.hip) that evaluate the same
+linear map without materialising any padded / up-sampled canvas, with a deterministic adjoint (``AugmentFn`` / ``AugmentAdjFn``,
+each the other's backward).  The host still samples G / C (same draws, same reflect-pad retry loop), computes the pads and
+fills the per-sample parameter block (``aug_params``).  The composed path stays for CPU tensors and other dtypes.
 """
 import math
 
+import numpy as np
 import torch
 import torch.nn.functional as F
+from torch.autograd import Function
 
 from .op import upfirdn2d
 
@@ -163,6 +170,156 @@ def random_apply_color(img, p, C=None):
 
 def augment(img, p, transform_matrix=(None, None)):
     """Same signature and return value as the reference: (augmented image, (G, C))."""
+    if img.is_cuda and img.dtype == torch.float32:
+        n, _, h, w = img.shape
+        G, pads = draw_affine(p, n, h, w, transform_matrix[0])
+        C = transform_matrix[1] if transform_matrix[1] is not None else sample_color(p, n)
+        return augment_fused(img, upload_params(aug_params(G, C, h, w, pads), img.device)), (G, C)
     img, G = random_apply_affine(img, p, transform_matrix[0])
     img, C = random_apply_color(img, p, transform_matrix[1])
     return img, (G, C)
+
+
+# ------------------------------------------------------------------------------------ fused path (HIP, host side)
+PAD_K = 6               # (len(SYM6) + 1) // 2: the reference's extra reflect pad on every side
+
+# rick_aug_param (include/rick_hip.h)
+PARAM_DTYPE = np.dtype([('a', '<f8', 6), ('ainv', '<f8', 4), ('col', '<f4', 12), ('py1', '<i4'), ('px1', '<i4'), ('hp', '<i4'),
+                        ('wp', '<i4')])
+assert PARAM_DTYPE.itemsize == 144
+
+
+def pads_ok(pads, height, width):
+    """F.pad(mode='reflect') with pad + PAD_K on each side succeeds iff every pad is smaller than its dimension."""
+    px1, px2, py1, py2 = pads
+    return max(px1, px2) + PAD_K < width and max(py1, py2) + PAD_K < height
+
+
+def draw_affine(p, n, height, width, G=None):
+    """G and its batch-maximum pads with the reference's retry loop (non_leaking.py:286-311): a G whose reflect pad would
+    raise is drawn again; a given G that fails raises, as the reference would retry forever."""
+    while True:
+        g = G if G is not None else sample_affine(p, n, height, width)
+        pads = _padding(torch.inverse(g.cpu().float()), height, width)
+        if pads_ok(pads, height, width):
+            return g, pads
+        if G is not None:
+            raise RuntimeError(f'augment: the given G needs reflect pads {pads} beyond a {height}x{width} image')
+
+
+def aug_params(G, C, height, width, pads):
+    """Host-side parameter block (numpy array of PARAM_DTYPE, one entry per sample) of one reference call: the warped-region ->
+    up-sampled canvas affine of random_apply_affine's sampling grid, the colour rows, the call's (batch-maximum) pads.
+    Several calls of one launch: concatenate their blocks."""
+    n = G.shape[0]
+    px1, px2, py1, py2 = pads
+    h, w = height, width
+    Hp, Wp = h + py1 + py2 + 2 * PAD_K, w + px1 + px2 + 2 * PAD_K
+    hp, wp = Hp - 2 * PAD_K + 1, Wp - 2 * PAD_K + 1             # (padded.shape - len_k + 1)
+    H2, W2 = 2 * Hp - 2 * PAD_K + 1, 2 * Wp - 2 * PAD_K + 1     # up-sampled canvas (= warped canvas) size
+    # linspace end points / steps of the grid (random_apply_affine), warped-canvas pixel (X, Y) = (2 px1 + c, 2 py1 + r)
+    xl, xh = -2 * px1 / w - 1, 2 * (wp - px1) / w - 1
+    yl, yh = -2 * py1 / h - 1, 2 * (hp - py1) / h - 1
+    dx, dy = (xh - xl) / (W2 - 1), (yh - yl) / (H2 - 1)
+    x0, y0 = xl + 2 * px1 * dx, yl + 2 * py1 * dy
+    # normalised grid -> up-sampled canvas pixels (grid_sample, align_corners=False): i = ((g + 1) * size - 1) / 2
+    kx, ky = w / wp * W2 / 2, h / hp * H2 / 2
+    lx, ly = (w + 2 * px1) / wp * W2 / 2 - 0.5, (h + 2 * py1) / hp * H2 / 2 - 0.5
+    m = torch.inverse(G.cpu().float())[:, :2, :].double().numpy()      # the reference inverts in fp32
+    out = np.zeros(n, PARAM_DTYPE)
+    a = out['a']
+    a[:, 0], a[:, 1] = kx * m[:, 0, 0] * dx, kx * m[:, 0, 1] * dy
+    a[:, 2] = kx * (m[:, 0, 0] * x0 + m[:, 0, 1] * y0 + m[:, 0, 2]) + lx
+    a[:, 3], a[:, 4] = ky * m[:, 1, 0] * dx, ky * m[:, 1, 1] * dy
+    a[:, 5] = ky * (m[:, 1, 0] * x0 + m[:, 1, 1] * y0 + m[:, 1, 2]) + ly
+    det = a[:, 0] * a[:, 4] - a[:, 1] * a[:, 3]
+    out['ainv'] = np.stack((a[:, 4] / det, -a[:, 1] / det, -a[:, 3] / det, a[:, 0] / det), 1)
+    out['col'] = C.cpu().float()[:, :3, :].reshape(n, 12).numpy()
+    out['py1'], out['px1'], out['hp'], out['wp'] = py1, px1, Hp, Wp
+    return out
+
+
+class ParamStaging:
+    """Pinned, double-buffered host staging for parameter blocks: a buffer is refilled only after the copy that last read it
+    has completed (its event), so an in-flight host-to-device copy is never overwritten."""
+
+    def __init__(self):
+        self.bufs, self.events, self.k = [None, None], [None, None], 0
+
+    def upload(self, block, dst):
+        raw = block.view(np.uint8).reshape(-1)
+        k = self.k = 1 - self.k
+        if self.events[k] is not None:
+            self.events[k].synchronize()
+        if self.bufs[k] is None or self.bufs[k].numel() < raw.size:
+            self.bufs[k] = torch.empty(max(raw.size, 4096), dtype=torch.uint8, pin_memory=True)
+        buf = self.bufs[k][:raw.size]
+        buf.numpy()[:] = raw
+        dst.view(-1)[:raw.size].copy_(buf, non_blocking=True)
+        ev = self.events[k] = torch.cuda.Event()
+        ev.record()
+        return dst
+
+
+_staging = ParamStaging()
+
+
+def upload_params(block, device, dst=None, staging=None):
+    """Copy a parameter block to the device: into `dst` (a persistent uint8 tensor that captured graphs read) or a new tensor."""
+    if dst is None:
+        dst = torch.empty(block.nbytes, dtype=torch.uint8, device=device)
+    elif dst.numel() < block.nbytes:
+        raise RuntimeError(f'augment: parameter block of {block.nbytes} bytes does not fit {dst.numel()}')
+    return (staging or _staging).upload(block, dst)
+
+
+def _launch(entry, x, params, **kw):
+    from ._lib import check, lib, ptr, require_cuda_f32, stream_ptr
+    require_cuda_f32(x)
+    x = x.contiguous()
+    n, c, h, w = x.shape
+    if c != 3 or params.numel() < n * PARAM_DTYPE.itemsize or not params.is_cuda:
+        raise RuntimeError(f'augment: needs [N, 3, H, W] images and N parameter entries; got {tuple(x.shape)}, {params.numel()} bytes')
+    ws = torch.empty(int(lib.rick_augment_workspace_floats(n, h, w)), device=x.device, dtype=torch.float32)
+    y = torch.empty_like(x)
+    if entry == 'fwd':
+        check(lib.rick_augment_fwd_f32(ptr(x), ptr(params), ptr(ws), ptr(y), n, h, w, int(kw['bias']), stream_ptr()),
+              'rick_augment_fwd_f32')
+    else:
+        check(lib.rick_augment_adj_f32(ptr(x), ptr(params), ptr(ws), ptr(y), n, h, w, stream_ptr()), 'rick_augment_adj_f32')
+    return y
+
+
+class AugmentFn(Function):
+    """y = augment(x) for fixed per-sample transforms (`bias`: with the colour offset).  Linear in x up to the offset: its
+    backward is AugmentAdjFn, whose backward is this map without the offset — closed under differentiation to any order.
+    No gradient flows to the parameters (the reference's matrices come from the sampler)."""
+
+    @staticmethod
+    def forward(ctx, x, params, bias=True):
+        ctx.save_for_backward(params)
+        return _launch('fwd', x, params, bias=bias)
+
+    @staticmethod
+    def backward(ctx, gy):
+        (params,) = ctx.saved_tensors
+        return AugmentAdjFn.apply(gy, params), None, None
+
+
+class AugmentAdjFn(Function):
+    """gx = (linear part of augment)^T gy."""
+
+    @staticmethod
+    def forward(ctx, gy, params):
+        ctx.save_for_backward(params)
+        return _launch('adj', gy, params)
+
+    @staticmethod
+    def backward(ctx, gg):
+        (params,) = ctx.saved_tensors
+        return AugmentFn.apply(gg, params, False), None
+
+
+def augment_fused(img, params):
+    """The augmentation of CUDA float32 [N, 3, H, W] images with a device parameter block of N rick_aug_param entries."""
+    return AugmentFn.apply(img, params, True)

@@ -59,8 +59,11 @@ def load_adam_state_dict(optim, sd):
 def state_dict(trainer):
     """The reference's checkpoint dict (:647-659) for a RickTrainer."""
     getattr(trainer, '_finish_pending', lambda: None)()      # a deferred optimiser step (data-parallel pipelining) lands first
-    return {'g_ema': trainer.g_ema.state_dict(), 'g': trainer.g.state_dict(), 'd': trainer.d.state_dict(),
-            'g_optim': adam_state_dict(trainer.g_optim), 'd_optim': adam_state_dict(trainer.d_optim)}
+    out = {'g_ema': trainer.g_ema.state_dict(), 'g': trainer.g.state_dict(), 'd': trainer.d.state_dict(),
+           'g_optim': adam_state_dict(trainer.g_optim), 'd_optim': adam_state_dict(trainer.d_optim)}
+    if getattr(getattr(trainer, 'cfg', None), 'augment', False):
+        out['ada_aug_p'] = float(trainer.ada_p)     # extra key of augmented runs: a resumed ADA run continues from its p
+    return out
 
 
 def save(trainer, path):
@@ -93,5 +96,8 @@ def resume(trainer, ckpt):
         load_adam_state_dict(trainer.g_optim, ckpt['g_optim'])
     if 'd_optim' in ckpt:
         load_adam_state_dict(trainer.d_optim, ckpt['d_optim'])
+    cfg = getattr(trainer, 'cfg', None)
+    if 'ada_aug_p' in ckpt and getattr(cfg, 'augment', False) and trainer.ada.adaptive:
+        trainer.ada_p = float(ckpt['ada_aug_p'])      # (a fixed augment_p > 0 stays what the run was configured with)
     trainer.invalidate_graphs()      # captured steps bake in the Adam run grouping of the old step counts
     return ckpt

@@ -19,6 +19,7 @@ from torch import autograd
 
 from . import op
 from ._lib import check, lib, ptr, stream_ptr
+from .augment import augment_fused
 
 
 # --------------------------------------------------------------------------- losses
@@ -354,6 +355,41 @@ class TrainConfig:
     prune_quantile: float = 0.1
     warmup_iter: int = 250
     ema_decay: float = 0.5 ** (32 / (10 * 1000))     # train_dynamic_update_prune.py:180
+    augment: bool = False                            # adaptive discriminator augmentation (:728-732)
+    augment_p: float = 0.0                           # > 0: fixed p; 0: p adapted from the sign of D's real logits
+    ada_target: float = 0.6
+    ada_length: int = 500 * 1000
+
+
+class AdaController:
+    """The adaptive augmentation probability of the reference (train_dynamic_update_prune.py:440-459): signs of D's real logits
+    are summed over steps; once more than 255 images are in, p moves by sign(mean - target) * ada_target / ada_length * n,
+    clamped to [0, 1], and the sums restart.  With augment_p > 0, p stays fixed.
+
+    The trainer keeps the sign sum on the device (no sync per step); the image count n is known on the host, so the device
+    value is read (and, under data parallelism, summed over ranks) only when n > 255."""
+
+    def __init__(self, cfg):
+        self.adaptive = cfg.augment_p == 0
+        self.p = float(cfg.augment_p) if cfg.augment_p > 0 else 0.0
+        self.step_size = cfg.ada_target / cfg.ada_length
+        self.target = cfg.ada_target
+        self.n = 0
+
+    def due(self, n_new):
+        """Count n_new more images; True when the sign sum must be read (n > 255)."""
+        if not self.adaptive:
+            return False
+        self.n += n_new
+        return self.n > 255
+
+    def update(self, sign_sum, n=None):
+        """Apply the accumulated statistic (sign_sum over self.n images, or over `n` when given); returns the new p."""
+        n = self.n if n is None else n
+        sign = 1 if sign_sum / n > self.target else -1
+        self.p = min(1.0, max(0.0, self.p + sign * self.step_size * n))
+        self.n = 0
+        return self.p
 
 
 def g_optim_filter(name):
@@ -395,6 +431,14 @@ class RickTrainer:
         self._gs, self._inject, self._layer_idx, self._real = {}, {}, None, None
         self._fisher_state = None   # persistent accumulators / static inputs / captured per-sample graph of the Fisher sweep
         self._pending = None        # (graph state, flat, optimiser, optimiser graph) of a step whose gradient exchange is in flight
+        # adaptive discriminator augmentation (cfg.augment): p, the device sign sum of D's real logits, the persistent device
+        # parameter blocks of the D / G steps (captured graphs read them; the host refills them before each step) and the D
+        # step's augmented reals (the R1 step's input).  `aug_source(n)`, when set, returns the (G, C) of a call of n images
+        # instead of the sampler (tests pin the transforms with it).
+        self.ada = AdaController(cfg)
+        self.aug_source = None
+        self._aug = {}
+        self._ada_sum = torch.zeros((), device=self.device) if cfg.augment and self.ada.adaptive else None
         if dp is not None:
             dp.attach(self.g_flat, self.d_flat)
 
@@ -463,7 +507,7 @@ class RickTrainer:
         self._real.copy_(real_img)
         for _ in range(3):
             self.d_step(self._real, None, graph=True)
-            self.r1_step(self._real, graph=True)
+            self.r1_step(self._aug_real if self.cfg.augment else self._real, graph=True)
             self.g_step(None, graph=True)
             self.plr_step(None, graph=True)
             self.ema_step()
@@ -676,11 +720,58 @@ class RickTrainer:
         self._fisher_state = None
         self.__dict__.pop('_lat_pool', None)                  # pooled W rows belong to the weights they were mapped with
 
+    # ---- adaptive discriminator augmentation
+    @property
+    def ada_p(self):
+        return self.ada.p
+
+    @ada_p.setter
+    def ada_p(self, v):
+        self.ada.p = float(v)
+
+    def _aug_block(self, key, n_calls, batch, reverse=False):
+        """Host side of the augmentation of a step (its `pre=` hook): one (G, C) draw per reference call, in the reference's
+        order, uploaded into the step's persistent device parameter block.  `n_calls` calls of `batch` images each; `reverse`:
+        the launch's images are in the opposite order of the draws."""
+        from . import augment as A
+        ent = self._aug.get(key)
+        h, w = self.cfg.size, self.cfg.size
+        if ent is None:
+            ent = self._aug[key] = {'dev': torch.zeros(n_calls * batch * A.PARAM_DTYPE.itemsize, dtype=torch.uint8,
+                                                       device=self.device), 'staging': A.ParamStaging()}
+        blocks = []
+        for _ in range(n_calls):
+            if self.aug_source is not None:
+                G, C = self.aug_source(batch)
+                G, pads = A.draw_affine(self.ada.p, batch, h, w, G)
+            else:
+                G, pads = A.draw_affine(self.ada.p, batch, h, w)
+                C = A.sample_color(self.ada.p, batch)
+            blocks.append(A.aug_params(G, C, h, w, pads))
+        A.upload_params(np.concatenate(blocks[::-1] if reverse else blocks), self.device, dst=ent['dev'], staging=ent['staging'])
+        ent['calls'] = blocks
+        return ent
+
+    def _ada_after_d_step(self, batch):
+        """Adaptive p (train_dynamic_update_prune.py:440-459) after a D step of `batch` images on this rank."""
+        if self._ada_sum is None:
+            return
+        world = getattr(self.dp, 'world', 1) if self.dp is not None else 1
+        if not self.ada.due(batch * world):
+            return
+        stat = self._ada_sum.view(1).clone()
+        if self.dp is not None and world > 1:
+            self.dp.all_reduce_vectors([stat])
+        self.ada.update(float(stat))
+        self._ada_sum.zero_()
+
     # ---- steps (each returns the loss tensor; no host sync)
     def d_step(self, real_img, noise, i=10 ** 9, g_noise=None, graph=False):
         self._set_d_stage(i)
         key = 'd' if graph else None
         batch = real_img.shape[0]
+
+        aug = self.cfg.augment
 
         def fb():
             with torch.no_grad():
@@ -688,19 +779,35 @@ class RickTrainer:
                     fake_img, _ = self.g([self._graph_latents(key, batch)], input_is_latent=True, noise=g_noise)
                 else:
                     fake_img, _ = self.g(noise, noise=g_noise)
+                x = torch.cat([fake_img, real_img], 0)
+                if aug:                          # augment(real), augment(fake) of the reference: one launch pair
+                    x = augment_fused(x, self._aug['d']['dev'])
+                    self._aug_real.copy_(x[batch:])           # the R1 step's input (a static buffer under graphs)
             # one pass over cat(fake, real): identical to the reference's two calls (per-call minibatch-stddev
             # statistics are kept), half the launches and twice the GEMM rows per launch
             with self._sink():                   # conv weight gradients are added straight into the flat buffer
-                pred, _ = self.d(torch.cat([fake_img, real_img], 0), calls=2)
+                pred, _ = self.d(x, calls=2)
                 fake_pred, real_pred = pred.chunk(2, 0)
                 d_loss = d_logistic_loss(real_pred, fake_pred)
+                if self._ada_sum is not None:
+                    self._ada_sum.add_(torch.sign(real_pred.detach()).sum())
                 self._zero_grad(self.d_flat)
                 # bias / noise-strength sums: one second-stage launch for the whole pass; (RICK_WGRAD_OVERLAP=1: sunk weight
                 # gradients on a second stream next to the data-gradient chain — measured slower, off by default, op/conv.py)
                 with op.deferred_sums(), op.wgrad_overlap():
                     d_loss.backward()
             self.losses.update(d=d_loss.detach(), real_score=real_pred.detach().mean(), fake_score=fake_pred.detach().mean())
-        self._run(key, fb, self.d_flat, self.d_optim, pre=(lambda: self._draw_inject(key)) if graph else None)
+
+        def pre():
+            if graph:
+                self._draw_inject(key)
+            if aug:
+                if getattr(self, '_aug_real', None) is None or self._aug_real.shape != real_img.shape:
+                    self._aug_real = torch.empty_like(real_img)
+                # the reference draws real's (G, C) first, then fake's; the launch runs over cat(fake, real)
+                self._aug_block('d', 2, batch, reverse=True)
+        self._run(key, fb, self.d_flat, self.d_optim, pre=pre if (graph or aug) else None)
+        self._ada_after_d_step(batch)
         return self.losses['d']
 
     def r1_step(self, real_img, i=10 ** 9, graph=False):
@@ -731,15 +838,25 @@ class RickTrainer:
                 else:
                     box['fake'], _ = self.g(noise, noise=g_noise)
 
+        aug = self.cfg.augment
+
         def fb():
             with self._sink(), self._d_frozen():
-                fake_pred, _ = self.d(box.pop('fake'))
+                fake = box.pop('fake')
+                if aug:
+                    fake = augment_fused(fake, self._aug['g']['dev'])
+                fake_pred, _ = self.d(fake)
                 g_loss = g_nonsaturating_loss(fake_pred)
                 self._zero_grad(self.g_flat)
                 with op.deferred_sums(), op.wgrad_overlap():
                     g_loss.backward()
             self.losses['g'] = g_loss.detach()
-        self._run(key, fb, self.g_flat, self.g_optim, pre=(lambda: self._draw_inject(key)) if graph else None, fb_head=head)
+        def pre():
+            if graph:
+                self._draw_inject(key)
+            if aug:
+                self._aug_block('g', 1, batch)
+        self._run(key, fb, self.g_flat, self.g_optim, pre=pre if (graph or aug) else None, fb_head=head)
         return self.losses['g']
 
     def _mixed_latents(self, noise):
@@ -884,8 +1001,8 @@ class RickTrainer:
         self._mark('begin')
         self.d_step(real_img, nz(cfg.batch), i, graph=graph)
         self._mark('d')
-        if i % cfg.d_reg_every == 0:
-            self.r1_step(real_img, i, graph=graph)
+        if i % cfg.d_reg_every == 0:       # with augmentation: the D step's augmented reals (:463-466)
+            self.r1_step(self._aug_real if cfg.augment else real_img, i, graph=graph)
             self._mark('r1')
         if i >= cfg.warmup_iter:
             self.g_step(nz(cfg.batch), graph=graph)
