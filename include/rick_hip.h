@@ -559,6 +559,32 @@ int rick_augment_fwd_f32(const float *x, const rick_aug_param *params, float *ws
                          void *stream);
 int rick_augment_adj_f32(const float *gy, const rick_aug_param *params, float *ws, float *gx, int N, int H, int W, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Inception — the torchvision InceptionV3 feature extractor up to pool3 (rick_amd/inception.py), the network behind
+ * the reference's FID (gan_training/metrics/inception.py).  Activations NHWC fp32; BatchNorm folded on the host.
+ * rick_inc_input_f32: planar images x [N, 3, H, W] -> bilinear resize to OH x OW (F.interpolate, align_corners=False)
+ *   and the ImageNet affine x * (std / 0.5) + (mean - 0.5) / 0.5 -> out [N, OH, OW, 4] (channel 3 = 0).
+ * rick_inc_conv_f32: out = relu(conv(in, W) + bias) as an implicit GEMM on the f32-input MFMA (exact fp32 products).
+ *   in [N, IH, IW, Ci] (Ci % 4 == 0); wpk [Kp][Cop] with K = KH*KW*Ci ordered (ky, kx, ci), Kp = K rounded up to 32,
+ *   Cop = Co rounded up to bn (64 or 128), zero-padded; bias [Cop].  Output columns [seg_start[s], seg_start[s+1]) go to
+ *   dst[s] + pixel * ldc[s] + c0[s] (a channel slice of a wider NHWC tensor: concats are free); seg_start[0] = 0, unused
+ *   slots >= Co.  Columns of one GEMM that read the same input (the fused 1x1 heads) are routed this way.
+ * rick_inc_maxpool_f32: 3x3 stride 2 max, no padding, [N, IH, IW, C] -> channels [c0, c0 + C) of an ldc-wide output.
+ * rick_inc_avgpool_f32: 3x3 stride 1 pad 1 average with count_include_pad, [N, H, W, C] -> same shape.
+ * rick_inc_mean_f32: [N, HW, C] -> [N, C] mean over HW in pixel order.
+ * No atomics: every output element has one writer and a fixed summation order (bit-identical from run to run). */
+typedef struct {
+    int N, IH, IW, Ci, KH, KW, SH, SW, PH, PW, OH, OW;
+    int Co, Cop, bn, nseg;
+    int seg_start[4], ldc[4], c0[4];
+    float *dst[4];
+} rick_inc_conv;
+int rick_inc_input_f32(const float *x, float *out, int N, int H, int W, int OH, int OW, void *stream);
+int rick_inc_conv_f32(const float *in, const float *wpk, const float *bias, const rick_inc_conv *a, void *stream);
+int rick_inc_maxpool_f32(const float *in, float *out, int N, int IH, int IW, int C, int ldc, int c0, void *stream);
+int rick_inc_avgpool_f32(const float *in, float *out, int N, int H, int W, int C, void *stream);
+int rick_inc_mean_f32(const float *in, float *out, int N, int HW, int C, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

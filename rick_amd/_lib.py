@@ -55,6 +55,12 @@ class SplitOut(ctypes.Structure):
                 ('adj_slope', c_f), ('adj_gain', c_f), ('adj_partials', c_fp)]
 
 
+class IncConv(ctypes.Structure):
+    """rick_inc_conv (include/rick_hip.h)."""
+    _fields_ = [(n, c_int) for n in ('N', 'IH', 'IW', 'Ci', 'KH', 'KW', 'SH', 'SW', 'PH', 'PW', 'OH', 'OW', 'Co', 'Cop', 'bn',
+                                     'nseg')] + [('seg_start', c_int * 4), ('ldc', c_int * 4), ('c0', c_int * 4), ('dst', c_fp * 4)]
+
+
 # name -> (restype, argtypes); every symbol declared in include/rick_hip.h
 SIGNATURES = {
     'rick_abi_version': (c_int, []),
@@ -159,6 +165,11 @@ SIGNATURES = {
     'rick_augment_workspace_floats': (c_i64, [c_int, c_int, c_int]),
     'rick_augment_fwd_f32': (c_int, [c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, c_fp]),
     'rick_augment_adj_f32': (c_int, [c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_fp]),
+    'rick_inc_input_f32': (c_int, [c_fp, c_fp, c_int, c_int, c_int, c_int, c_int, c_fp]),
+    'rick_inc_conv_f32': (c_int, [c_fp, c_fp, c_fp, ctypes.POINTER(IncConv), c_fp]),
+    'rick_inc_maxpool_f32': (c_int, [c_fp, c_fp, c_int, c_int, c_int, c_int, c_int, c_int, c_fp]),
+    'rick_inc_avgpool_f32': (c_int, [c_fp, c_fp, c_int, c_int, c_int, c_int, c_fp]),
+    'rick_inc_mean_f32': (c_int, [c_fp, c_fp, c_int, c_int, c_int, c_fp]),
 }
 
 if not os.path.exists(LIB_PATH):
