@@ -585,6 +585,34 @@ int rick_inc_maxpool_f32(const float *in, float *out, int N, int IH, int IW, int
 int rick_inc_avgpool_f32(const float *in, float *out, int N, int H, int W, int C, void *stream);
 int rick_inc_mean_f32(const float *in, float *out, int N, int HW, int C, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * LPIPS — lpips 0.1 with the VGG16 backbone (rick_amd/lpips.py), the metric behind the reference's intra-cluster LPIPS
+ * (gan_training/eval.py).  The 13 convolutions run on rick_inc_conv_f32; activations and taps are NHWC fp32.
+ * rick_lpips_input_f32: planar [N, 3, H, W] -> out [N, H, W, 4] (channel 3 = 0) through lpips' scaling layer
+ *   (x - shift) / scale.  mode 0: float x as is.  mode 1: float x through the reference's PNG round trip,
+ *   q = uint8(clamp((x / 2 + 0.5) * 255 + 0.5, 0, 255)), then (q / 255 - 0.5) / 0.5; q is also written to u8out (planar,
+ *   may be NULL).  mode 2: uint8 xq, then (q / 255 - 0.5) / 0.5.  Every step is one correctly rounded fp32 operation.
+ * rick_lpips_maxpool2_f32: 2x2 stride 2 max with floor, [N, IH, IW, C] -> [N, IH / 2, IW / 2, C] (C % 4 == 0).
+ * rick_lpips_invnorm_f32: in [P, C] -> out[p] = 1 / (sqrt(sum_c in[p, c]^2) + 1e-10); 0 where the sum is 0.
+ * rick_lpips_pair_f32: one tap of two image sets, fa [na, HW, C] with inverse norms ia [na, HW], fb / ib likewise, lin
+ *   weights w [C] (C <= 1024) -> part[s][i][j] (fp64) = sum over the positions [s pps, (s + 1) pps) of slice s and all
+ *   channels of w_c (fa_ic ia_i - fb_jc ib_j)^2, for s < ceil(HW / pps).  Summation order depends on (position, channel)
+ *   only: d(x, x) = 0 and D(A, B) = D(B, A)^T exactly, and a pair's value does not depend on the other images of the call.
+ * rick_lpips_reduce_f32: part = the nlayers taps' partials one after the other ([nslices[l]][na][nb] each) -> out [na, nb]
+ *   fp32 = sum over taps in order of (sum over slices in order) / hw[l], in fp64.
+ * No atomics: every output element has one writer and a fixed summation order. */
+typedef struct {
+    int nlayers;
+    int nslices[8], hw[8];
+} rick_lpips_layers;
+int rick_lpips_input_f32(const float *x, const uint8_t *xq, float *out, uint8_t *u8out, int N, int H, int W, int mode,
+                         void *stream);
+int rick_lpips_maxpool2_f32(const float *in, float *out, int N, int IH, int IW, int C, void *stream);
+int rick_lpips_invnorm_f32(const float *in, float *out, int64_t P, int C, void *stream);
+int rick_lpips_pair_f32(const float *fa, const float *ia, int na, const float *fb, const float *ib, int nb, const float *w,
+                        int HW, int C, int pps, double *part, void *stream);
+int rick_lpips_reduce_f32(const double *part, float *out, int na, int nb, const rick_lpips_layers *d, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

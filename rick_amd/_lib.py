@@ -61,6 +61,11 @@ class IncConv(ctypes.Structure):
                                      'nseg')] + [('seg_start', c_int * 4), ('ldc', c_int * 4), ('c0', c_int * 4), ('dst', c_fp * 4)]
 
 
+class LpipsLayers(ctypes.Structure):
+    """rick_lpips_layers (include/rick_hip.h)."""
+    _fields_ = [('nlayers', c_int), ('nslices', c_int * 8), ('hw', c_int * 8)]
+
+
 # name -> (restype, argtypes); every symbol declared in include/rick_hip.h
 SIGNATURES = {
     'rick_abi_version': (c_int, []),
@@ -170,6 +175,11 @@ SIGNATURES = {
     'rick_inc_maxpool_f32': (c_int, [c_fp, c_fp, c_int, c_int, c_int, c_int, c_int, c_int, c_fp]),
     'rick_inc_avgpool_f32': (c_int, [c_fp, c_fp, c_int, c_int, c_int, c_int, c_fp]),
     'rick_inc_mean_f32': (c_int, [c_fp, c_fp, c_int, c_int, c_int, c_fp]),
+    'rick_lpips_input_f32': (c_int, [c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, c_fp]),
+    'rick_lpips_maxpool2_f32': (c_int, [c_fp, c_fp, c_int, c_int, c_int, c_int, c_fp]),
+    'rick_lpips_invnorm_f32': (c_int, [c_fp, c_fp, c_i64, c_int, c_fp]),
+    'rick_lpips_pair_f32': (c_int, [c_fp, c_fp, c_int, c_fp, c_fp, c_int, c_fp, c_int, c_int, c_int, c_fp, c_fp]),
+    'rick_lpips_reduce_f32': (c_int, [c_fp, c_fp, c_int, c_int, ctypes.POINTER(LpipsLayers), c_fp]),
 }
 
 if not os.path.exists(LIB_PATH):

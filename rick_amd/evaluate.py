@@ -6,8 +6,13 @@ NumPy until ``n_sample_test`` images exist; FID is then computed by a third-part
 network (weights are a download: out of scope here).  This module keeps the
 sampling loop on the device: the same batches, images written into one preallocated tensor, no
 host round trips.  A feature extractor can be plugged in through ``feature_fn`` (called per
-batch on device tensors) so a metric never needs the images on the host either.
+batch on device tensors) so a metric never needs the images on the host either.  ``intra_lpips`` is the
+reference's intra-cluster LPIPS (eval.py:83-190) on the device, over rick_amd.lpips.
 """
+import math
+import os
+
+import numpy as np
 import torch
 
 
@@ -194,6 +199,118 @@ def precision_recall_from_features(feats_real, feats_fake, k=3, block=4096):
     return covered(xr, radii(xr), xf), covered(xf, radii(xf), xr)
 
 
+def lpips_sample_count(n_samples=1000, n_sample_store=25, fid_sample_size=5000):
+    """Images the reference's compute_intra_lpips keeps (eval.py:86-92): whole batches of ``n_sample_store`` until at
+    least ``n_samples`` exist, then the first ``fid_sample_size``."""
+    return min(-(-n_samples // n_sample_store) * n_sample_store, fid_sample_size)
+
+
+def assign_clusters(dist):
+    """dist [n, K] (sample-to-centre LPIPS) -> [n] int64: the nearest centre, ties to the lowest index (np.argmin)."""
+    return torch.from_numpy(np.argmin(np.asarray(torch.as_tensor(dist).cpu(), dtype=np.float64), axis=1).astype(np.int64))
+
+
+def cluster_subsets(assign, k, cluster_size=50, rng=None):
+    """Members of each of the k clusters in sample order; a cluster with more than ``cluster_size`` members keeps
+    ``members[torch.randperm(count, generator=rng)[:cluster_size]]``.  The reference shuffles a directory listing with
+    ``random.shuffle`` (eval.py:170-171), which no seed reproduces; a torch.Generator makes the draw reproducible."""
+    assign = torch.as_tensor(assign).cpu()
+    out = []
+    for c in range(k):
+        idx = torch.nonzero(assign == c).flatten()
+        if idx.numel() > cluster_size:
+            idx = idx[torch.randperm(idx.numel(), generator=rng)[:cluster_size]]
+        out.append(idx)
+    return out
+
+
+def mean_pair_distance(d):
+    """Mean of d[i, j] over the unordered pairs i < j of a square distance matrix (fp64); NaN below two members."""
+    d = torch.as_tensor(d).to('cpu', torch.float64)
+    m = d.shape[0]
+    if m < 2:
+        return math.nan
+    iu = torch.triu_indices(m, m, 1)
+    return float(d[iu[0], iu[1]].mean())
+
+
+def nan_mean(values):
+    """Mean of the non-NaN values (eval.py:189); NaN if there are none."""
+    v = torch.as_tensor(values, dtype=torch.float64)
+    v = v[~torch.isnan(v)]
+    return float(v.mean()) if v.numel() else math.nan
+
+
+@torch.no_grad()
+def intra_lpips(g_ema, centers, lpips, n_samples=1000, n_sample_store=25, cluster_size=50, fid_sample_size=5000, latent=512,
+                size=256, latents=None, rng=None):
+    """Intra-cluster LPIPS (gan_training/eval.py:83-190) on the device -> (value, per_cluster [K] fp64 with NaN, counts [K]).
+
+    centers: uint8 [K, 3, size, size] (``load_cluster_centers``); lpips: a ``rick_amd.lpips.LPIPS``.  The samples go through
+    the reference's PNG round trip (uint8, read back as q / 255) and stay on the device as uint8.  Pass 1: each batch's
+    LPIPS features, its distances to the K centres (whose features are computed once), then the nearest centre of every
+    sample.  Pass 2: per cluster, at most ``cluster_size`` members (``cluster_subsets``, drawn from ``rng``), their features
+    recomputed from the stored uint8 images (bit-identical to pass 1's: the trunk is batch-invariant) and the mean LPIPS over
+    all their unordered pairs.  ``value`` is the mean over the clusters with at least two members (NaN if none).  Images
+    whose size is not ``size`` are refused, as the reference's Resize([256, 256]) is the identity only there."""
+    dev = next(g_ema.parameters()).device
+    if centers.dim() != 4 or centers.shape[1] != 3 or tuple(centers.shape[2:]) != (size, size):
+        raise ValueError(f'intra_lpips: centres must be [K, 3, {size}, {size}], got {tuple(centers.shape)}')
+    if centers.dtype != torch.uint8:
+        raise ValueError(f'intra_lpips: centres must be uint8 (the PNG files), got {centers.dtype}')
+    n = lpips_sample_count(n_samples, n_sample_store, fid_sample_size)
+    K = centers.shape[0]
+    fc = lpips.features(centers.to(dev).contiguous())
+    store = torch.empty((n, 3, size, size), device=dev, dtype=torch.uint8)
+    dist = torch.empty((n, K), device=dev, dtype=torch.float32)
+    ws = lpips.workspace_features if dev.type == 'cuda' and n_sample_store <= lpips.batch and lpips.size == size else None
+    was_training = g_ema.training
+    g_ema.eval()
+    done = 0
+    while done < n:
+        if latents is not None:
+            z = latents[done:done + n_sample_store].to(dev)
+            if z.shape[0] == 0:
+                raise RuntimeError('intra_lpips: not enough fixed latents')
+        else:
+            z = torch.randn(n_sample_store, latent, device=dev)
+        img, _ = g_ema([z])
+        if tuple(img.shape[2:]) != (size, size):
+            raise ValueError(f'intra_lpips: generated images are {tuple(img.shape[2:])}, the evaluation size is {size}')
+        take = min(img.shape[0], n - done)
+        f = lpips.features(img[:take].contiguous(), quantize=True, out=ws, u8_out=store[done:done + take])
+        dist[done:done + take] = lpips.distances(f, fc)
+        done += take
+    if was_training:
+        g_ema.train()
+    assign = assign_clusters(dist)
+    counts = torch.bincount(assign, minlength=K)
+    per = torch.full((K,), math.nan, dtype=torch.float64)
+    subsets = cluster_subsets(assign, K, cluster_size, rng)
+    fs = None
+    for c, idx in enumerate(subsets):
+        if idx.numel() < 2:
+            continue
+        if fs is None and dev.type == 'cuda':
+            fs = lpips.new_features(max(s.numel() for s in subsets), size, size)
+        f = lpips.features(store[idx.to(dev)], out=fs)
+        per[c] = mean_pair_distance(lpips.distances(f, f))
+    return nan_mean(per), per, counts
+
+
+def load_cluster_centers(root, k=10):
+    """The reference's cluster centres (``../cluster_centers/<data>/<method>/c{i}/center.png``, eval.py:122-124) -> uint8
+    [k, 3, S, S], decoded with rick_amd.data.decode_png."""
+    from .data import decode_png
+    imgs = []
+    for i in range(k):
+        with open(os.path.join(root, f'c{i}', 'center.png'), 'rb') as fh:
+            imgs.append(decode_png(fh.read()))
+    if len({im.shape for im in imgs}) != 1:
+        raise ValueError(f'load_cluster_centers: centres of different sizes {sorted({im.shape for im in imgs})}')
+    return torch.from_numpy(np.stack(imgs)).permute(0, 3, 1, 2).contiguous()
+
+
 class Evaluator:
     """Device-resident counterpart of ``gan_training.eval.Evaluator`` (eval.py:13-66).
 
@@ -247,3 +364,9 @@ class Evaluator:
             ff = torch.cat(pr_feats, 0)[:self.sample_size] if pr_feats else fake
             score['precision'], score['recall'] = precision_recall_from_features(fr, ff, k=self.k)
         return score
+
+    def compute_intra_lpips(self, centers, lpips, n_samples=1000, cluster_size=50, size=256, latents=None, rng=None):
+        """The reference's ``compute_intra_lpips(args)`` (eval.py:83-107) -> the intra-cluster LPIPS (see ``intra_lpips``)."""
+        return intra_lpips(self.generator, centers, lpips, n_samples=n_samples, n_sample_store=self.n_sample_store,
+                           cluster_size=cluster_size, fid_sample_size=self.sample_size, latent=self.latent, size=size,
+                           latents=latents, rng=rng)[0]
