@@ -613,6 +613,30 @@ int rick_lpips_pair_f32(const float *fa, const float *ia, int na, const float *f
                         int HW, int C, int pps, double *part, void *stream);
 int rick_lpips_reduce_f32(const double *part, float *out, int na, int nb, const rick_lpips_layers *d, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * VGG16 fc2 — the features behind the reference's improved precision / recall (rick_amd/vgg.py;
+ * gan_metrics/precision_recall.py:124-152, IPR.extract_features, called from gan_training/eval.py:58-65).  The 13
+ * convolutions of vgg16.features run on rick_inc_conv_f32 and its five 2x2 max pools on rick_lpips_maxpool2_f32 (the last
+ * one, 14^2 -> 7^2, included); activations are NHWC fp32.
+ * rick_vgg_input_f32: planar x [N, 3, H, W] -> out [N, 224, 224, 4] (channel 3 = 0), the reference's
+ *   F.interpolate(size=(224, 224)) (precision_recall.py:135-139, 146; default mode 'nearest'): source index
+ *   min(int(floorf(dst * (float(in) / float(out)))), in - 1) with the scale in fp32; the identity at 224.  Values are copied:
+ *   there is no affine on this path.
+ * rick_fc_f32: out[M, N] = act(x[M, K] W^T + bias), 1 <= M <= 64, act = ReLU if relu else identity: classifier[0] + [1] and
+ *   classifier[3] of precision_recall.py:149 (Dropout is the identity in eval).  f32-input MFMA, exact fp32 products.
+ *   wpk = W [N, K] packed once as [Np / 32][Kp / 8][64 lanes][4] (rick_fc_packed_floats(K, N) floats, Np = N rounded up to
+ *   128, Kp = K rounded up to 8, zero padded): lane (h = lane >> 5, c = lane & 31) of column block nb and k block kb holds
+ *   W[32 nb + c][8 kb + 2 j + h] in component j.  Stage 1 writes split-K partials ws[s][m][n] (rick_fc_workspace_floats(M, K,
+ *   N) floats; the slicing is a function of (K, N) only), each the sum of two fp32 fma chains, over the even and over the odd k blocks of the
+ *   slice, in the order k block ascending, j ascending, h ascending; stage 2 sums the slices in order, adds the bias and applies the activation.
+ *   Row m of out is bit-identical whatever M is and whatever the other rows hold.  x rows are contiguous (stride K).
+ * No atomics: every output element has one writer and a fixed summation order (bit-identical from run to run). */
+int rick_vgg_input_f32(const float *x, float *out, int N, int H, int W, void *stream);
+int64_t rick_fc_packed_floats(int K, int N);
+int64_t rick_fc_workspace_floats(int M, int K, int N);
+int rick_fc_f32(const float *x, const float *wpk, const float *bias, float *ws, float *out, int M, int K, int N, int relu,
+                void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -180,6 +180,10 @@ SIGNATURES = {
     'rick_lpips_invnorm_f32': (c_int, [c_fp, c_fp, c_i64, c_int, c_fp]),
     'rick_lpips_pair_f32': (c_int, [c_fp, c_fp, c_int, c_fp, c_fp, c_int, c_fp, c_int, c_int, c_int, c_fp, c_fp]),
     'rick_lpips_reduce_f32': (c_int, [c_fp, c_fp, c_int, c_int, ctypes.POINTER(LpipsLayers), c_fp]),
+    'rick_vgg_input_f32': (c_int, [c_fp, c_fp, c_int, c_int, c_int, c_fp]),
+    'rick_fc_packed_floats': (c_i64, [c_int, c_int]),
+    'rick_fc_workspace_floats': (c_i64, [c_int, c_int, c_int]),
+    'rick_fc_f32': (c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, c_fp]),
 }
 
 if not os.path.exists(LIB_PATH):

@@ -33,16 +33,13 @@ and the lin weights file (``lin{k}.model.1.weight``, the layout of lpips' ``weig
 import ctypes
 
 import torch
-import torch.nn.functional as F
+
+from .vgg_trunk import CHANNELS, STAGES, VggTrunk, cpu_stages
 
 SHIFT = (-.030, -.088, -.188)
 SCALE = (.458, .448, .450)
 EPS = 1e-10
 SIZE = 256
-# (features index, Ci, Co) of the 13 convolutions, grouped by tap; a 2x2 max pool precedes every stage but the first
-STAGES = [[(0, 3, 64), (2, 64, 64)], [(5, 64, 128), (7, 128, 128)], [(10, 128, 256), (12, 256, 256), (14, 256, 256)],
-          [(17, 256, 512), (19, 512, 512), (21, 512, 512)], [(24, 512, 512), (26, 512, 512), (28, 512, 512)]]
-CHANNELS = (64, 128, 256, 512, 512)
 TAPS = (3, 8, 15, 22, 29)
 SLICE_OF = {idx: s + 1 for s, stage in enumerate(STAGES) for idx, _, _ in stage}     # lpips' net.slice{1..5}
 PAIR_SLICE_ELEMS = 8192      # feature elements per pair-kernel slice: positions per slice = 8192 // C, fixed per tap
@@ -184,16 +181,7 @@ def scale_input(x, quantize=False):
     return (x - shift) / scale, q
 
 
-def _cpu_taps(convs, x):
-    taps = []
-    for s, stage in enumerate(STAGES):
-        if s:
-            x = F.max_pool2d(x, 2, 2)
-        for idx, _, _ in stage:
-            w, b = convs[idx]
-            x = F.relu(F.conv2d(x, w, b, 1, 1))
-        taps.append(x)
-    return taps
+_cpu_taps = cpu_stages            # the five taps are the five stage outputs of the shared trunk
 
 
 def _inverse_norm(f, dim):
@@ -202,54 +190,16 @@ def _inverse_norm(f, dim):
 
 
 class _Plan:
-    """Workspace of `batch` images at size x size and the packed convolution weights (device)."""
+    """Workspace of `batch` images at size x size and the shared trunk's packed convolution weights (device)."""
 
     def __init__(self, convs, lins, batch, size, device):
         from . import _lib
         self._lib = _lib
         self.batch, self.size, self.pixels = batch, size, batch * size * size
-        f32 = dict(device=device, dtype=torch.float32)
-        # ping-pong capacity per level-0 pixel: walk the stages (ping <- pool / first conv, alternate within a stage)
-        need, area = [0.0, 0.0], 1.0
-        for s, stage in enumerate(STAGES):
-            if s:
-                area /= 4
-                need[0] = max(need[0], area * stage[0][1])          # pool output
-                cur = 0
-            else:
-                cur = None
-            for k, (_, _, co) in enumerate(stage[:-1]):
-                dst = 0 if cur is None else 1 - cur
-                need[dst] = max(need[dst], area * co)
-                cur = dst
-        self.x0 = torch.empty(self.pixels * 4, **f32)
-        self.bufs = [torch.empty(int(self.pixels * need[0]), **f32), torch.empty(max(1, int(self.pixels * need[1])), **f32)]
-        self.w, self.convs = [], []
-        for stage in STAGES:
-            for idx, ci, co in stage:
-                w, b = convs[idx]
-                cip = -(-ci // 4) * 4
-                if cip != ci:                                       # the 3 input channels, padded to 4
-                    w = F.pad(w, (0, 0, 0, 0, 0, cip - ci))
-                K, bn = 9 * cip, 64 if co == 64 else 128
-                Kp, Cop = -(-K // 32) * 32, -(-co // bn) * bn
-                wpk = torch.zeros(Kp, Cop, dtype=torch.float32)
-                wpk[:K, :co] = w.permute(2, 3, 1, 0).reshape(K, co)
-                bp = torch.zeros(Cop, dtype=torch.float32)
-                bp[:co] = b
-                self.convs.append((cip, co, Cop, bn, wpk.to(device), bp.to(device)))
+        self.trunk = VggTrunk(convs, device)
+        self.x0 = torch.empty(self.pixels * 4, device=device, dtype=torch.float32)
+        self.bufs = self.trunk.new_buffers(self.pixels, device)
         self.lins = [w.to(device) for w in lins]
-
-    def _conv(self, k, src, n, h, w, dst):
-        lib = self._lib
-        ci, co, cop, bn, wpk, bp = self.convs[k]
-        a = lib.IncConv()
-        a.N, a.IH, a.IW, a.Ci, a.KH, a.KW, a.SH, a.SW, a.PH, a.PW, a.OH, a.OW = n, h, w, ci, 3, 3, 1, 1, 1, 1, h, w
-        a.Co, a.Cop, a.bn, a.nseg = co, cop, bn, 1
-        for i in range(4):
-            a.seg_start[i], a.ldc[i], a.c0[i], a.dst[i] = (0, co, 0, dst) if i == 0 else (co, 0, 0, None)
-        lib.check(lib.lib.rick_inc_conv_f32(src, wpk.data_ptr(), bp.data_ptr(), ctypes.byref(a), lib.stream_ptr()),
-                  'rick_inc_conv_f32')
 
     def run(self, x, mode, out, u8out):
         """x [n, 3, H, W] (fp32, or uint8 for mode 2), n * H * W <= pixels -> the taps of out (an LpipsFeatures of n)."""
@@ -259,21 +209,11 @@ class _Plan:
         xf, xq = (None, x.data_ptr()) if mode == 2 else (x.data_ptr(), None)
         lib.check(lib.lib.rick_lpips_input_f32(xf, xq, self.x0.data_ptr(), u8out.data_ptr() if u8out is not None else None,
                                                n, H, W, mode, stream), 'rick_lpips_input_f32')
-        cur, h, w, k = self.x0.data_ptr(), H, W, 0
-        for s, stage in enumerate(STAGES):
-            if s:
-                c = CHANNELS[s - 1]
-                lib.check(lib.lib.rick_lpips_maxpool2_f32(cur, self.bufs[0].data_ptr(), n, h, w, c, stream),
-                          'rick_lpips_maxpool2_f32')
-                cur, h, w, flip = self.bufs[0].data_ptr(), h // 2, w // 2, 1
-            else:
-                flip = 0
-            for j in range(len(stage)):
-                dst = out.taps[s].data_ptr() if j == len(stage) - 1 else self.bufs[flip].data_ptr()
-                self._conv(k, cur, n, h, w, dst)
-                cur, flip, k = dst, 1 - flip, k + 1
-            lib.check(lib.lib.rick_lpips_invnorm_f32(cur, out.inorm[s].data_ptr(), n * h * w, CHANNELS[s], stream),
+
+        def invnorm(s, tap, n, h, w):
+            lib.check(lib.lib.rick_lpips_invnorm_f32(tap, out.inorm[s].data_ptr(), n * h * w, CHANNELS[s], stream),
                       'rick_lpips_invnorm_f32')
+        self.trunk.run(self.x0.data_ptr(), n, H, W, self.bufs, lambda s: out.taps[s].data_ptr(), invnorm)
 
 
 class LPIPS:
