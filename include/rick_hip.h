@@ -291,7 +291,8 @@ int rick_conv_tuning(int key, int value);
 /* Producers.  rick_upfirdn2d_f32 / rick_upfirdn2d_act_f32 (tail may be NULL) with the extended result handling, channels-last
  * only; `out` may be NULL with ex->no_f32.  The activation adjoint (rick_bias_act_bwd_f32) leaving as split images:
  * out1 = g * (ref > 0 ? 1 : alpha) * scale and, when out2 != NULL, out2 = g * mul2 (the same gradient entering a parallel linear
- * branch), both bounded through *amax_g >= max |g|.  The ResBlock merge y = (a + b) * alpha (rick_add_scale_f32) written as
+ * branch), both bounded through *amax_g >= max |g|; any C % 4 == 0 with 16-byte aligned g / ref / images (the layout of
+ * rick_split_pack_f32 — the consumers check their own C % 32), RICK_EINVAL otherwise.  The ResBlock merge y = (a + b) * alpha (rick_add_scale_f32) written as
  * fp32 and as a split image. */
 int rick_upfirdn2d_ex_f32(const float *input, const float *kernel, float *out,
                           int64_t major, int in_h, int in_w, int minor, int kh, int kw,

@@ -528,7 +528,9 @@ extern "C" int rick_bias_act_bwd_split2_f32(const float *g, const float *ref, vo
                                             float alpha, float scale, float *partials, int accumulate, void *stream);
 
 // The activation adjoint written as split images: out1 = g * (ref > 0 ? 1 : alpha) * scale (bound |scale| * *amax_g) and,
-// when out2 != NULL, out2 = g * mul2 (bound |mul2| * *amax_g).  C % 32 == 0; gb / gnw as in rick_bias_act_bwd_f32.
+// when out2 != NULL, out2 = g * mul2 (bound |mul2| * *amax_g).  C % 4 == 0 and 16-byte aligned pointers, as rick_split_pack_f32
+// (an image is 16 bytes per four channels at the float4's own address: cv_split_store4; the MFMA consumers check their own
+// C % 32); gb / gnw as in rick_bias_act_bwd_f32.
 extern "C" int rick_bias_act_bwd_split_f32(const float *g, const float *ref, void *out1, float *hdr1, void *out2, float *hdr2,
                                            float mul2, const float *amax_g, float *gb, float *gnw, const float *noise,
                                            int64_t rows, int C, int64_t rows_per_img, int64_t noise_nb, int64_t noise_hw,
