@@ -573,6 +573,18 @@ int rick_augment_adj_f32(const float *gy, const rick_aug_param *params, float *w
  * rick_inc_maxpool_f32: 3x3 stride 2 max, no padding, [N, IH, IW, C] -> channels [c0, c0 + C) of an ldc-wide output.
  * rick_inc_avgpool_f32: 3x3 stride 1 pad 1 average with count_include_pad, [N, H, W, C] -> same shape.
  * rick_inc_mean_f32: [N, HW, C] -> [N, C] mean over HW in pixel order.
+ * rick_inc_input_raw_f32: rick_inc_input_f32's resize without the affine, for the Inception Score's network
+ *   (gan_training/metrics/inception_score.py: inception_v3(transform_input=False) on the images as they are, or after
+ *   nn.Upsample(size=(299, 299), mode='bilinear')).  At OH == H and OW == W it copies the values bit for bit.
+ * rick_is_rows_f32: logits [M, C] (C >= 1) -> p [M, C] fp32 = softmax of each row as F.softmax forms it (subtract the row
+ *   maximum, expf, divide by the fp32 sum), and per row in fp64 s[m] = sum_c p[m, c] and h[m] = sum_c q log q with
+ *   q = p / s[m]; a term with p == 0 is exactly 0.  One wave per row: lane l adds the classes l, l + 64, ... in ascending
+ *   order (lanes past C hold -inf for the maximum and 0 for the sums), then a 32, 16, ..., 1 xor butterfly.
+ * rick_is_accum_f64: folds the M rows of one call into the statistic acc [S][2 C + 1] fp64: per split the class sums of p,
+ *   the class sums of q = p / s and the sum of h.  The call's row i is row g = row0 + i of the sample and belongs to split
+ *   g / per (per = N_total / S); rows with g >= S * per are ignored.  One thread owns one (split, column) accumulator and adds
+ *   the call's rows in ascending order onto the stored value: the state after the whole sample is bit-identical however the
+ *   sample was cut into calls.  acc starts as zeros.
  * No atomics: every output element has one writer and a fixed summation order (bit-identical from run to run). */
 typedef struct {
     int N, IH, IW, Ci, KH, KW, SH, SW, PH, PW, OH, OW;
@@ -585,6 +597,10 @@ int rick_inc_conv_f32(const float *in, const float *wpk, const float *bias, cons
 int rick_inc_maxpool_f32(const float *in, float *out, int N, int IH, int IW, int C, int ldc, int c0, void *stream);
 int rick_inc_avgpool_f32(const float *in, float *out, int N, int H, int W, int C, void *stream);
 int rick_inc_mean_f32(const float *in, float *out, int N, int HW, int C, void *stream);
+int rick_inc_input_raw_f32(const float *x, float *out, int N, int H, int W, int OH, int OW, void *stream);
+int rick_is_rows_f32(const float *logits, float *p, double *s, double *h, int M, int C, void *stream);
+int rick_is_accum_f64(const float *p, const double *s, const double *h, double *acc, int M, int C, int S, int64_t row0,
+                      int64_t per, void *stream);
 
 /* ---------------------------------------------------------------------------------------
  * LPIPS — lpips 0.1 with the VGG16 backbone (rick_amd/lpips.py), the metric behind the reference's intra-cluster LPIPS

@@ -175,6 +175,9 @@ SIGNATURES = {
     'rick_inc_maxpool_f32': (c_int, [c_fp, c_fp, c_int, c_int, c_int, c_int, c_int, c_int, c_fp]),
     'rick_inc_avgpool_f32': (c_int, [c_fp, c_fp, c_int, c_int, c_int, c_int, c_fp]),
     'rick_inc_mean_f32': (c_int, [c_fp, c_fp, c_int, c_int, c_int, c_fp]),
+    'rick_inc_input_raw_f32': (c_int, [c_fp, c_fp, c_int, c_int, c_int, c_int, c_int, c_fp]),
+    'rick_is_rows_f32': (c_int, [c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_fp]),
+    'rick_is_accum_f64': (c_int, [c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_i64, c_i64, c_fp]),
     'rick_lpips_input_f32': (c_int, [c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, c_fp]),
     'rick_lpips_maxpool2_f32': (c_int, [c_fp, c_fp, c_int, c_int, c_int, c_int, c_fp]),
     'rick_lpips_invnorm_f32': (c_int, [c_fp, c_fp, c_i64, c_int, c_fp]),

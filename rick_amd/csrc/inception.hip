@@ -13,6 +13,9 @@ typedef float inc_f32x16 __attribute__((ext_vector_type(16)));
 #define IC_AS (IC_BM + 1)  // A tile row stride in floats: the [k][row] transpose writes hit 32 distinct banks
 
 // ---- input: bilinear resize (F.interpolate, align_corners=False, no antialias) + ImageNet affine, NCHW -> NHWC4 ------------
+// AFFINE = false (the Inception Score's network, which sees the images as they are): no affine, and a plain copy where the
+// output size is the input size (the interpolation formula would turn -0 into +0).
+template <bool AFFINE>
 __global__ __launch_bounds__(256) void inc_input_kernel(const float *__restrict__ x, float *__restrict__ out, int N, int H, int W,
                                                         int OH, int OW, float sh, float sw) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -30,8 +33,12 @@ __global__ __launch_bounds__(256) void inc_input_kernel(const float *__restrict_
 #pragma unroll
     for (int c = 0; c < 3; c++) {
         const float *p = x + ((int64_t)n * 3 + c) * H * W;
+        if (!AFFINE && OH == H && OW == W) {
+            r[c] = p[oy * W + ox];
+            continue;
+        }
         const float v = hy * (hx * p[y0 * W + x0] + lx * p[y0 * W + x1]) + ly * (hx * p[y1 * W + x0] + lx * p[y1 * W + x1]);
-        r[c] = v * mul[c] + add[c];
+        r[c] = AFFINE ? v * mul[c] + add[c] : v;
     }
     reinterpret_cast<float4 *>(out)[i] = make_float4(r[0], r[1], r[2], 0.f);
 }
@@ -218,13 +225,93 @@ __global__ __launch_bounds__(256) void inc_mean_kernel(const float *__restrict__
     out[i] = s / (float)HW;
 }
 
+// ---- Inception Score: softmax rows and the streamed statistic -----------------------------------------------------------
+// same butterfly as wave_sum (common.h): every lane ends with the same bits
+__device__ __forceinline__ float is_wave_max(float v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
+    return v;
+}
+__device__ __forceinline__ double is_wave_sum_f64(double v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+// One wave per row.  Lane l owns the classes l, l + 64, ... and adds them in ascending order; lanes past C hold the identity
+// (-inf for the max, 0 for the sums).  p = expf(x - max) / (fp32 sum), s = sum p and h = sum q log q (q = p / s) in fp64.
+__global__ __launch_bounds__(256) void is_rows_kernel(const float *__restrict__ logits, float *__restrict__ p, double *__restrict__ s,
+                                                      double *__restrict__ h, int M, int C) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (row >= M) return;                                     // wave-uniform
+    const float *x = logits + (int64_t)row * C;
+    float *pr = p + (int64_t)row * C;
+    float mx = -INFINITY;
+    for (int c = lane; c < C; c += 64) mx = fmaxf(mx, x[c]);
+    mx = is_wave_max(mx);
+    float den = 0.f;
+    for (int c = lane; c < C; c += 64) den += expf(x[c] - mx);
+    den = wave_sum(den);
+    double sv = 0.0;
+    for (int c = lane; c < C; c += 64) {
+        const float v = expf(x[c] - mx) / den;
+        pr[c] = v;
+        sv += (double)v;
+    }
+    sv = is_wave_sum_f64(sv);
+    double hv = 0.0;
+    for (int c = lane; c < C; c += 64) {
+        const float v = pr[c];                                // this thread's own store
+        if (v > 0.f) {
+            const double q = (double)v / sv;
+            hv += q * log(q);
+        }
+    }
+    hv = is_wave_sum_f64(hv);
+    if (lane == 0) {
+        s[row] = sv;
+        h[row] = hv;
+    }
+}
+
+// One thread per accumulator (split k, column j) of acc [S][2C + 1]: j < C the class sum of p, j < 2C the class sum of
+// q = p / s, j = 2C the sum of h.  Global row g = row0 + i belongs to split g / per; the thread adds its split's rows of this
+// call in ascending order onto the stored value, so the chain of additions is the same however the sample is cut into calls.
+__global__ __launch_bounds__(256) void is_accum_kernel(const float *__restrict__ p, const double *__restrict__ s,
+                                                       const double *__restrict__ h, double *__restrict__ acc, int M, int C, int S,
+                                                       int64_t row0, int64_t per) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int W = 2 * C + 1;
+    if (i >= (int64_t)S * W) return;
+    const int j = (int)(i % W);
+    const int64_t k = i / W;
+    const int64_t lo = k * per > row0 ? k * per - row0 : 0;
+    const int64_t hi = (k + 1) * per - row0 < M ? (k + 1) * per - row0 : M;
+    if (lo >= hi) return;
+    double a = acc[i];
+    for (int64_t r = lo; r < hi; r++) {
+        if (j < C) a += (double)p[r * C + j];
+        else if (j < 2 * C) a += (double)p[r * C + (j - C)] / s[r];
+        else a += h[r];
+    }
+    acc[i] = a;
+}
+
 static unsigned inc_grid(int64_t n) { return (unsigned)((n + 255) / 256); }
 
 extern "C" int rick_inc_input_f32(const float *x, float *out, int N, int H, int W, int OH, int OW, void *stream) {
     if (!x || !out || N < 0 || H <= 0 || W <= 0 || OH <= 0 || OW <= 0 || ((uintptr_t)out % 16)) return RICK_EINVAL;
     if (N == 0) return 0;
-    hipLaunchKernelGGL(inc_input_kernel, dim3(inc_grid((int64_t)N * OH * OW)), dim3(256), 0, (hipStream_t)stream, x, out, N, H, W,
-                       OH, OW, (float)H / (float)OH, (float)W / (float)OW);
+    hipLaunchKernelGGL(inc_input_kernel<true>, dim3(inc_grid((int64_t)N * OH * OW)), dim3(256), 0, (hipStream_t)stream, x, out, N,
+                       H, W, OH, OW, (float)H / (float)OH, (float)W / (float)OW);
+    RICK_LAUNCH_STATUS();
+}
+
+extern "C" int rick_inc_input_raw_f32(const float *x, float *out, int N, int H, int W, int OH, int OW, void *stream) {
+    if (!x || !out || N < 0 || H <= 0 || W <= 0 || OH <= 0 || OW <= 0 || ((uintptr_t)out % 16)) return RICK_EINVAL;
+    if (N == 0) return 0;
+    hipLaunchKernelGGL(inc_input_kernel<false>, dim3(inc_grid((int64_t)N * OH * OW)), dim3(256), 0, (hipStream_t)stream, x, out, N,
+                       H, W, OH, OW, (float)H / (float)OH, (float)W / (float)OW);
     RICK_LAUNCH_STATUS();
 }
 
@@ -280,5 +367,21 @@ extern "C" int rick_inc_mean_f32(const float *in, float *out, int N, int HW, int
     if (!in || !out || N < 0 || HW <= 0 || C <= 0) return RICK_EINVAL;
     if (N == 0) return 0;
     hipLaunchKernelGGL(inc_mean_kernel, dim3(inc_grid((int64_t)N * C)), dim3(256), 0, (hipStream_t)stream, in, out, N, HW, C);
+    RICK_LAUNCH_STATUS();
+}
+
+extern "C" int rick_is_rows_f32(const float *logits, float *p, double *s, double *h, int M, int C, void *stream) {
+    if (!logits || !p || !s || !h || M < 0 || C < 1) return RICK_EINVAL;
+    if (M == 0) return 0;
+    hipLaunchKernelGGL(is_rows_kernel, dim3((unsigned)cdiv(M, 4)), dim3(256), 0, (hipStream_t)stream, logits, p, s, h, M, C);
+    RICK_LAUNCH_STATUS();
+}
+
+extern "C" int rick_is_accum_f64(const float *p, const double *s, const double *h, double *acc, int M, int C, int S, int64_t row0,
+                                 int64_t per, void *stream) {
+    if (!p || !s || !h || !acc || M < 0 || C < 1 || C > (1 << 29) || S < 1 || row0 < 0 || per < 1) return RICK_EINVAL;
+    if (M == 0) return 0;
+    hipLaunchKernelGGL(is_accum_kernel, dim3(inc_grid((int64_t)S * (2 * C + 1))), dim3(256), 0, (hipStream_t)stream, p, s, h, acc, M,
+                       C, S, row0, per);
     RICK_LAUNCH_STATUS();
 }

@@ -3,11 +3,14 @@
 The reference's ``Evaluator.compute_inception_score`` (gan_training/eval.py:31-46) draws
 ``n_sample_store`` latents at a time, runs ``g_ema([z])`` and moves every image to the host as
 NumPy until ``n_sample_test`` images exist; FID is then computed by a third-party Inception
-network (weights are a download: out of scope here).  This module keeps the
+network (rick_amd.inception runs it on the device; its weights are a download and are supplied by
+the user).  This module keeps the
 sampling loop on the device: the same batches, images written into one preallocated tensor, no
 host round trips.  A feature extractor can be plugged in through ``feature_fn`` (called per
 batch on device tensors) so a metric never needs the images on the host either.  ``intra_lpips`` is the
-reference's intra-cluster LPIPS (eval.py:83-190) on the device, over rick_amd.lpips.
+reference's intra-cluster LPIPS (eval.py:83-190) on the device, over rick_amd.lpips.  ``InceptionScoreStats`` /
+``inception_score`` are the reference's Inception Score (gan_training/metrics/inception_score.py) streamed on the
+device over rick_amd.inception.InceptionV3Logits; ``Evaluator.compute_inception_score(iscore=True)`` reports it.
 """
 import math
 import os
@@ -199,6 +202,87 @@ def precision_recall_from_features(feats_real, feats_fake, k=3, block=4096):
     return covered(xr, radii(xr), xf), covered(xf, radii(xf), xr)
 
 
+class InceptionScoreStats:
+    """The Inception Score (gan_training/metrics/inception_score.py:12-58) streamed on the device.
+
+    The reference stores softmax(logits) of all N images in a float64 [N, 1000] host array, cuts it into ``splits`` runs of
+    ``per = N // splits`` rows (the rest is dropped) and returns the mean and population std over the splits of
+    exp(mean_i KL(p_i || py)), with scipy.stats.entropy renormalising both arguments.  Here every batch is reduced at once
+    to a state [splits, 2 C + 1] fp64: per split the class sums P of p, the class sums Q of q_i = p_i / sum_c p_ic and
+    H = sum_i sum_c q_ic log q_ic.  With n = per, py = P / n and qy = py / sum py the split's score is
+    exp(H / n - sum_c (Q_c / n) log qy_c), the same quantity.  On the device the rows come from rick_is_rows_f32 and are
+    folded by rick_is_accum_f64, which adds rows in ascending order: the state does not depend on how the sample was cut
+    into batches.  CPU tensors take the same steps in torch.
+
+    net: images -> logits [N, C] (``rick_amd.inception.InceptionV3Logits``); n_total: the N of the reference's call."""
+
+    def __init__(self, net, n_total, splits=1):
+        if splits < 1:
+            raise ValueError(f'InceptionScoreStats: splits must be >= 1, got {splits}')
+        if n_total // splits < 1:
+            raise ValueError(f'InceptionScoreStats: {n_total} samples cannot fill {splits} splits')
+        self.net, self.n_total, self.splits, self.per = net, int(n_total), int(splits), int(n_total) // int(splits)
+        self.seen, self.acc = 0, None
+
+    @torch.no_grad()
+    def update_logits(self, logits):
+        """Fold logits [M, C] fp32, the next M rows of the sample."""
+        if logits.dim() != 2 or logits.dtype != torch.float32:
+            raise RuntimeError(f'InceptionScoreStats: expected fp32 logits [M, C], got {logits.dtype} {tuple(logits.shape)}')
+        M, C = logits.shape
+        if self.acc is None:
+            self.acc = torch.zeros((self.splits, 2 * C + 1), device=logits.device, dtype=torch.float64)
+        if self.acc.shape[1] != 2 * C + 1 or self.acc.device != logits.device:
+            raise RuntimeError(f'InceptionScoreStats: the state is {tuple(self.acc.shape)} on {self.acc.device}, got logits '
+                               f'{tuple(logits.shape)} on {logits.device}')
+        if logits.device.type == 'cpu':
+            p = torch.softmax(logits, dim=-1)
+            s = p.double().sum(1)
+            q = p.double() / s[:, None]
+            h = torch.xlogy(q, q).sum(1)
+            for i in range(M):                                  # ascending rows, one at a time: the kernel's order
+                g = self.seen + i
+                if g < self.splits * self.per:
+                    k = g // self.per
+                    self.acc[k, :C] += p[i].double()
+                    self.acc[k, C:2 * C] += q[i]
+                    self.acc[k, 2 * C] += h[i]
+        else:
+            from .inception import accumulate_rows, softmax_rows
+            p, s, h = softmax_rows(logits)
+            accumulate_rows(self.acc, p, s, h, self.seen, self.per)
+        self.seen += M
+        return self
+
+    @torch.no_grad()
+    def update(self, images):
+        """Push a batch of images through the network and fold its rows; nothing leaves the device."""
+        return self.update_logits(self.net(images))
+
+    @torch.no_grad()
+    def finalize(self):
+        """-> (mean, std) over the splits as fp64 0-dim tensors on the state's device (std: population, 0 for one split)."""
+        if self.acc is None or self.seen < self.splits * self.per:
+            raise RuntimeError(f'InceptionScoreStats: {self.seen} of {self.splits * self.per} samples seen')
+        C, n = (self.acc.shape[1] - 1) // 2, float(self.per)
+        P, Q, H = self.acc[:, :C], self.acc[:, C:2 * C], self.acc[:, 2 * C]
+        py = P / n
+        qy = py / py.sum(1, keepdim=True)
+        scores = torch.exp(H / n - torch.xlogy(Q / n, qy).sum(1))
+        return scores.mean(), scores.std(unbiased=False)
+
+
+@torch.no_grad()
+def inception_score(images, net, splits=1):
+    """The reference's ``inception_score(imgs, resize=..., splits=...)`` on an image tensor [N, 3, H, W] -> (mean, std);
+    whether the images are resized is a property of ``net`` (``InceptionV3Logits.load(size=...)``)."""
+    stats = InceptionScoreStats(net, images.shape[0], splits)
+    step = int(getattr(net, 'batch', 100))
+    for lo in range(0, images.shape[0], step):
+        stats.update(images[lo:lo + step])
+    return stats.finalize()
+
+
 def lpips_sample_count(n_samples=1000, n_sample_store=25, fid_sample_size=5000):
     """Images the reference's compute_intra_lpips keeps (eval.py:86-92): whole batches of ``n_sample_store`` until at
     least ``n_samples`` exist, then the first ``fid_sample_size``."""
@@ -323,7 +407,8 @@ class Evaluator:
     ``pr_feature_fn`` / ``real_pr_feats`` to keep that split)."""
 
     def __init__(self, generator, feature_fn, real_feats, n_sample_store=25, latent=512, inception_nsamples=5000,
-                 fid_sample_size=5000, pr_feature_fn=None, real_pr_feats=None, k=3):
+                 fid_sample_size=5000, pr_feature_fn=None, real_pr_feats=None, k=3, is_net=None):
+        self.is_net = is_net
         self.generator, self.feature_fn, self.real_feats = generator, feature_fn, real_feats
         self.n_sample_store, self.latent = n_sample_store, latent
         self.inception_nsamples, self.sample_size, self.k = inception_nsamples, fid_sample_size, k
@@ -331,10 +416,20 @@ class Evaluator:
 
     @torch.no_grad()
     def compute_inception_score(self, fid=True, kid=False, pr=False, latents=None, kid_subsets=100, kid_subset_size=1000,
-                                rng=None):
-        """-> dict with 'fid', 'kid', 'precision', 'recall' (the keys the reference fills, eval.py:44-66)."""
+                                rng=None, iscore=False, is_splits=1):
+        """-> dict with 'fid', 'kid', 'precision', 'recall' (the keys the reference fills, eval.py:44-66); iscore=True adds
+        'is' and 'is_std', the Inception Score of the first ``fid_sample_size`` generated images over ``is_splits`` splits
+        (``is_net``: a ``rick_amd.inception.InceptionV3Logits``), streamed batch by batch through InceptionScoreStats."""
         g = self.generator
         dev = next(g.parameters()).device
+        is_stats = None
+        if iscore:
+            if self.is_net is None:
+                raise RuntimeError('Evaluator: iscore=True needs is_net')
+            n_gen = -(-self.inception_nsamples // self.n_sample_store) * self.n_sample_store
+            if latents is not None:
+                n_gen = min(n_gen, latents.shape[0])
+            is_stats = InceptionScoreStats(self.is_net, min(n_gen, self.sample_size), is_splits)
         was_training = g.training
         g.eval()
         feats, pr_feats, done = [], [], 0
@@ -347,6 +442,8 @@ class Evaluator:
             feats.append(self.feature_fn(img).reshape(img.shape[0], -1))
             if pr and self.pr_feature_fn is not None:
                 pr_feats.append(self.pr_feature_fn(img).reshape(img.shape[0], -1))
+            if is_stats is not None and done < is_stats.n_total:
+                is_stats.update(img[:is_stats.n_total - done])
             done += img.shape[0]
         if was_training:
             g.train()
@@ -363,6 +460,8 @@ class Evaluator:
             fr = self.real_pr_feats.to(dev) if self.real_pr_feats is not None else real
             ff = torch.cat(pr_feats, 0)[:self.sample_size] if pr_feats else fake
             score['precision'], score['recall'] = precision_recall_from_features(fr, ff, k=self.k)
+        if is_stats is not None:
+            score['is'], score['is_std'] = is_stats.finalize()
         return score
 
     def compute_intra_lpips(self, centers, lpips, n_samples=1000, cluster_size=50, size=256, latents=None, rng=None):

@@ -14,6 +14,17 @@ the weights are loaded.  CUDA fp32 inputs run the HIP kernels of rick_amd/csrc/i
 f32-input MFMA implicit GEMM per convolution, the 1x1 heads that share an input fused into one GEMM, concats written in
 place); CPU inputs run the same folded network as a plain fp32 torch composition.  The CUDA path is capture-safe at a
 fixed N: the workspace is allocated once in ``load``, every launch goes to the caller's stream, branches run in order.
+
+``InceptionV3Logits`` is the same trunk with torchvision's classifier head, the network behind the reference's Inception Score
+(gan_training/metrics/inception_score.py): ``inception_v3(transform_input=False)`` on the images as they are, or after a
+bilinear resize to 299 x 299, then pool3 -> ``fc`` 2048 -> 1000.
+
+    net = InceptionV3Logits.load(src, device='cuda', batch=100, size=None)      # size=(H, W): no resize, that size only
+    logits = net(images)       # [N, 1000] fp32
+    p = net.probs(images)      # fp32 softmax of the rows
+
+The launch plan takes its geometry from the input size (75 x 75 at least, torchvision's floor; H and W may differ) and sizes
+its buffers from a dry walk over the layer table.
 """
 import ctypes
 import re
@@ -136,7 +147,8 @@ def fold(sd, last_block=3):
 
 
 # ---- CPU: the folded network as an fp32 torch composition ---------------------------------------------------------------
-def _cpu_forward(P, x, last_block):
+def _cpu_forward(P, x, last_block, affine=True):
+    """affine=True: the FID wrapper's resize to 299 and ImageNet affine first; False: the blocks on x as it is."""
     def conv(name, v, s=(1, 1), p=(0, 0)):
         w, b = P[name]
         return F.relu(F.conv2d(v, w, b, s, p))
@@ -147,8 +159,9 @@ def _cpu_forward(P, x, last_block):
     def pool(v):
         return F.avg_pool2d(v, 3, 1, 1, count_include_pad=True)
 
-    x = F.interpolate(x, (SIZE, SIZE), mode='bilinear', align_corners=False)
-    x = torch.cat([x[:, c:c + 1] * (STD[c] / 0.5) + (MEAN[c] - 0.5) / 0.5 for c in range(3)], 1)
+    if affine:
+        x = F.interpolate(x, (SIZE, SIZE), mode='bilinear', align_corners=False)
+        x = torch.cat([x[:, c:c + 1] * (STD[c] / 0.5) + (MEAN[c] - 0.5) / 0.5 for c in range(3)], 1)
     for u in STEM0:
         x = unit(u, x)
     x = F.max_pool2d(x, 3, 2)
@@ -194,48 +207,64 @@ def _out_hw(h, w, k, s, p):
     return (h + 2 * p[0] - k[0]) // s[0] + 1, (w + 2 * p[1] - k[1]) // s[1] + 1
 
 
-class _Plan:
-    """Buffers and launches of one network at batch `batch`.  Each step is f(n, stream)."""
+MIN_SIZE = 75                   # torchvision's floor: below it a stride-2 stage has no output left
 
-    def __init__(self, P, last_block, batch, device):
+
+class _Plan:
+    """Buffers and launches of one network at batch `batch` on inputs resized to (or given at) in_hw = (H, W).  Each step is
+    f(n, stream).  The layer table is walked twice: a dry walk that only records how many floats each buffer must hold (the
+    two ping-pong buffers and every scratch key), then, with the buffers allocated at those sizes, the walk that packs the
+    weights and records the launches."""
+
+    def __init__(self, P, last_block, batch, device, in_hw=(SIZE, SIZE), input_kernel='rick_inc_input_f32'):
         from . import _lib
         self._lib = _lib
         self.dev, self.batch, self.steps, self.keep = device, batch, [], []
-        B = batch
+        self.in_hw, self.input_kernel = (int(in_hw[0]), int(in_hw[1])), input_kernel
+        if min(self.in_hw) < MIN_SIZE:
+            raise ValueError(f'InceptionV3: the network needs an input of at least {MIN_SIZE} x {MIN_SIZE}, got {self.in_hw}')
         f32 = dict(device=device, dtype=torch.float32)
-        self.x0 = torch.empty(B * SIZE * SIZE * 4, **f32)
-        big = B * 147 * 147 * 64                      # largest activation (Conv2d_2b_3x3's output)
-        bufs = [torch.empty(big, **f32), torch.empty(big, **f32)]
-        self.keep += bufs
-        tmp = {}
+        self._need, self._bufs = {}, None
+        self._walk(P, last_block)                      # dry: sizes only
+        self._bufs = {k: torch.empty(n, **f32) for k, n in self._need.items()}
+        self.keep += list(self._bufs.values())
+        self.x0 = self._bufs['x0']
+        self.final, self.final_hw, self.final_c = self._walk(P, last_block)
 
-        def scratch(key, numel):
-            t = tmp.get(key)
-            if t is None or t.numel() < numel:
-                t = tmp[key] = torch.empty(numel, **f32)
-                self.keep.append(t)
-            return t
+    def _buf(self, key, numel):
+        """The buffer `key`, holding at least `numel` floats (dry walk: its key, and the size is recorded)."""
+        if self._bufs is None:
+            self._need[key] = max(self._need.get(key, 0), numel)
+            return key
+        assert self._bufs[key].numel() >= numel
+        return self._bufs[key]
 
+    def _walk(self, P, last_block):
+        B = self.batch
+        scratch = self._buf
         # stem: x0 -> 1a -> 2a -> 2b -> maxpool -> (3b -> 4a -> maxpool)
-        cur, h, w, c = self.x0, SIZE, SIZE, 4
+        (h, w), c = self.in_hw, 4
+        cur = self._buf('x0', B * h * w * 4)
         flip = 0
         for stem in ([STEM0] + ([STEM1] if last_block >= 1 else [])):
             for u in stem:
-                dst = bufs[flip]
                 oh, ow = _out_hw(h, w, u[3], u[4], u[5])
+                dst = self._buf(('pp', flip), B * oh * ow * u[2])
                 self._conv([u], P, cur, h, w, c, [(dst, u[2], 0)])
                 cur, h, w, c, flip = dst, oh, ow, u[2], 1 - flip
-            dst = bufs[flip]
+            oh, ow = (h - 3) // 2 + 1, (w - 3) // 2 + 1
+            dst = self._buf(('pp', flip), B * oh * ow * c)
             self._maxpool(cur, h, w, c, dst, c, 0)
-            cur, h, w, flip = dst, (h - 3) // 2 + 1, (w - 3) // 2 + 1, 1 - flip
+            cur, h, w, flip = dst, oh, ow, 1 - flip
         for kind, name, cin, par in MIXED:
             if MIXED_BLOCK[name] > last_block:
                 break
             U = {u[0].split('.', 1)[1]: u for u in mixed_units(kind, name, cin, par)}
-            out = bufs[flip]
             hw = h * w
+            oh, ow = _out_hw(h, w, (3, 3), (2, 2), (0, 0)) if kind in ('B', 'D') else (h, w)
+            co = {'A': 224 + (par or 0), 'B': 480 + c, 'C': 768, 'D': 512 + c, 'E': 2048}[kind]
+            out = self._buf(('pp', flip), B * oh * ow * co)
             if kind == 'A':
-                co = 224 + par
                 t5, d1, d2 = scratch('a5', B * hw * 48), scratch('ad1', B * hw * 64), scratch('ad2', B * hw * 96)
                 self._conv([U['branch1x1'], U['branch5x5_1'], U['branch3x3dbl_1']], P, cur, h, w, c,
                            [(out, co, 0), (t5, 48, 0), (d1, 64, 0)])
@@ -245,10 +274,7 @@ class _Plan:
                 pl = scratch('pool', B * hw * c)
                 self._avgpool(cur, h, w, c, pl)
                 self._conv([U['branch_pool']], P, pl, h, w, c, [(out, co, 224)])
-                oh, ow = h, w
             elif kind == 'B':
-                co = 480 + c
-                oh, ow = _out_hw(h, w, (3, 3), (2, 2), (0, 0))
                 d1, d2 = scratch('ad1', B * hw * 64), scratch('ad2', B * hw * 96)
                 self._conv([U['branch3x3']], P, cur, h, w, c, [(out, co, 0)])
                 self._conv([U['branch3x3dbl_1']], P, cur, h, w, c, [(d1, 64, 0)])
@@ -256,7 +282,7 @@ class _Plan:
                 self._conv([U['branch3x3dbl_3']], P, d2, h, w, 96, [(out, co, 384)])
                 self._maxpool(cur, h, w, c, out, co, 480)
             elif kind == 'C':
-                co, c7 = 768, par
+                c7 = par
                 ta, tb = scratch('c7a', B * hw * 192), scratch('c7b', B * hw * 192)
                 da, db = scratch('cda', B * hw * 192), scratch('cdb', B * hw * 192)
                 self._conv([U['branch1x1'], U['branch7x7_1'], U['branch7x7dbl_1']], P, cur, h, w, c,
@@ -270,10 +296,7 @@ class _Plan:
                 pl = scratch('pool', B * hw * c)
                 self._avgpool(cur, h, w, c, pl)
                 self._conv([U['branch_pool']], P, pl, h, w, c, [(out, co, 576)])
-                oh, ow = h, w
             elif kind == 'D':
-                co = 512 + c
-                oh, ow = _out_hw(h, w, (3, 3), (2, 2), (0, 0))
                 t3, ta, tb = scratch('c7a', B * hw * 192), scratch('cda', B * hw * 192), scratch('cdb', B * hw * 192)
                 self._conv([U['branch3x3_1'], U['branch7x7x3_1']], P, cur, h, w, c, [(t3, 192, 0), (ta, 192, 0)])
                 self._conv([U['branch3x3_2']], P, t3, h, w, 192, [(out, co, 0)])
@@ -282,7 +305,6 @@ class _Plan:
                 self._conv([U['branch7x7x3_4']], P, ta, h, w, 192, [(out, co, 320)])
                 self._maxpool(cur, h, w, c, out, co, 512)
             else:
-                co = 2048
                 t3, d1, d2 = scratch('e3', B * hw * 384), scratch('ed1', B * hw * 448), scratch('ed2', B * hw * 384)
                 self._conv([U['branch1x1'], U['branch3x3_1'], U['branch3x3dbl_1']], P, cur, h, w, c,
                            [(out, co, 0), (t3, 384, 0), (d1, 448, 0)])
@@ -294,15 +316,16 @@ class _Plan:
                 pl = scratch('pool', B * hw * c)
                 self._avgpool(cur, h, w, c, pl)
                 self._conv([U['branch_pool']], P, pl, h, w, c, [(out, co, 1856)])
-                oh, ow = h, w
             cur, h, w, c, flip = out, oh, ow, co, 1 - flip
-        self.final, self.final_hw, self.final_c = cur, h * w, c
+        return cur, h * w, c
 
     def _conv(self, us, P, src, h, w, ci, dsts):
         """One GEMM for the units `us` (same input, same geometry); dsts[i] = (tensor, ldc, c0) of unit i."""
         lib = self._lib
         k, s, p = us[0][3], us[0][4], us[0][5]
         assert all(u[3] == k and u[4] == s and u[5] == p for u in us)
+        if self._bufs is None:
+            return
         ws = []
         for u in us:
             wt = P[u[0]][0]
@@ -343,11 +366,15 @@ class _Plan:
         self.steps.append(run)
 
     def _maxpool(self, src, h, w, c, dst, ldc, c0):
+        if self._bufs is None:
+            return
         lib, sp, dp = self._lib, src.data_ptr(), dst.data_ptr()
         self.steps.append(lambda n, stream: lib.check(lib.lib.rick_inc_maxpool_f32(sp, dp, n, h, w, c, ldc, c0, stream),
                                                       'rick_inc_maxpool_f32'))
 
     def _avgpool(self, src, h, w, c, dst):
+        if self._bufs is None:
+            return
         lib, sp, dp = self._lib, src.data_ptr(), dst.data_ptr()
         self.steps.append(lambda n, stream: lib.check(lib.lib.rick_inc_avgpool_f32(sp, dp, n, h, w, c, stream),
                                                       'rick_inc_avgpool_f32'))
@@ -357,7 +384,8 @@ class _Plan:
         lib = self._lib
         n, _, H, W = x.shape
         stream = lib.stream_ptr()
-        lib.check(lib.lib.rick_inc_input_f32(x.data_ptr(), self.x0.data_ptr(), n, H, W, SIZE, SIZE, stream), 'rick_inc_input_f32')
+        lib.check(getattr(lib.lib, self.input_kernel)(x.data_ptr(), self.x0.data_ptr(), n, H, W, self.in_hw[0], self.in_hw[1],
+                                                      stream), self.input_kernel)
         for step in self.steps:
             step(n, stream)
         lib.check(lib.lib.rick_inc_mean_f32(self.final.data_ptr(), out.data_ptr(), n, self.final_hw, self.final_c, stream),
@@ -409,3 +437,147 @@ class InceptionV3Features:
                 hi = min(N, lo + self.batch)
                 self._plan.run(x[lo:hi], out[lo:hi])
         return out
+
+
+# ---- the classifier head: the Inception Score's network ------------------------------------------------------------------
+CLASSES, POOL3 = 1000, 2048
+
+
+def fc_from_state_dict(sd):
+    """(fc.weight [1000, 2048], fc.bias [1000]) fp32 on the CPU; a missing or mis-shaped key is an error that names it."""
+    out = []
+    for key, shape in (('fc.weight', (CLASSES, POOL3)), ('fc.bias', (CLASSES,))):
+        if key not in sd:
+            raise KeyError(f'InceptionV3Logits: missing key {key!r}')
+        v = torch.as_tensor(sd[key])
+        if tuple(v.shape) != shape:
+            raise ValueError(f'InceptionV3Logits: key {key!r} has shape {tuple(v.shape)}, expected {shape}')
+        out.append(v.detach().to('cpu', torch.float32).contiguous())
+    return tuple(out)
+
+
+def softmax_rows(logits):
+    """logits [M, C] fp32 on the device -> (p [M, C] fp32, s [M] fp64, h [M] fp64) by rick_is_rows_f32: the fp32 softmax, its
+    fp64 row sums and the rows' sum q log q with q = p / s."""
+    from . import _lib as lib
+    lib.require_cuda_f32(logits)
+    if logits.dim() != 2 or logits.shape[1] < 1:
+        raise RuntimeError(f'softmax_rows: expected logits [M, C], got {tuple(logits.shape)}')
+    x = logits.detach().contiguous()
+    M, C = x.shape
+    p = torch.empty_like(x)
+    s = torch.empty(M, device=x.device, dtype=torch.float64)
+    h = torch.empty(M, device=x.device, dtype=torch.float64)
+    with torch.cuda.device(x.device):
+        lib.check(lib.lib.rick_is_rows_f32(x.data_ptr(), p.data_ptr(), s.data_ptr(), h.data_ptr(), M, C, lib.stream_ptr()),
+                  'rick_is_rows_f32')
+    return p, s, h
+
+
+def accumulate_rows(acc, p, s, h, row0, per):
+    """Fold the rows (p, s, h) of softmax_rows, rows row0 ... of the sample, into acc [S, 2 C + 1] fp64 (rick_is_accum_f64)."""
+    from . import _lib as lib
+    M, C = p.shape
+    if acc.dtype != torch.float64 or not acc.is_contiguous() or acc.dim() != 2 or acc.shape[1] != 2 * C + 1:
+        raise RuntimeError(f'accumulate_rows: acc must be contiguous fp64 [S, {2 * C + 1}], got {acc.dtype} {tuple(acc.shape)}')
+    if not (p.is_contiguous() and s.is_contiguous() and h.is_contiguous()) or s.numel() != M or h.numel() != M:
+        raise RuntimeError('accumulate_rows: p [M, C], s [M] and h [M] must be contiguous')
+    if not (p.device == s.device == h.device == acc.device) or s.dtype != torch.float64 or h.dtype != torch.float64:
+        raise RuntimeError('accumulate_rows: p fp32, s and h fp64, all on the device of acc')
+    lib.require_cuda_f32(p)
+    with torch.cuda.device(p.device):
+        lib.check(lib.lib.rick_is_accum_f64(p.data_ptr(), s.data_ptr(), h.data_ptr(), acc.data_ptr(), M, C, acc.shape[0],
+                                            int(row0), int(per), lib.stream_ptr()), 'rick_is_accum_f64')
+
+
+class InceptionV3Logits:
+    """torchvision's Inception3 (eval, transform_input=False) up to its logits: images [N, 3, H, W] -> [N, 1000] fp32.
+
+    size=None: the images are resized to 299 x 299 (bilinear, align_corners=False), the reference's resize=True.
+    size=(H, W): they are taken as they are and must have that size (resize=False)."""
+
+    def __init__(self, folded, fc, device='cuda', batch=100, size=None):
+        if batch < 1:
+            raise ValueError('InceptionV3Logits: batch must be >= 1')
+        self.folded, self.fc, self.batch = folded, fc, int(batch)
+        self.size = None if size is None else (int(size[0]), int(size[1]))
+        if self.size is not None and min(self.size) < MIN_SIZE:
+            raise ValueError(f'InceptionV3Logits: size must be at least {MIN_SIZE} x {MIN_SIZE}, got {self.size}')
+        self.classes = CLASSES
+        self.device = torch.device(device)
+        self._plan = None
+        if self.device.type == 'cuda':
+            from . import _lib
+            from .fc import FC_MAX_ROWS, pack_fc_weight
+            if self.device.index is None:
+                self.device = torch.device('cuda', torch.cuda.current_device())
+            with torch.cuda.device(self.device):
+                self._plan = _Plan(folded, 3, self.batch, self.device, in_hw=self.size or (SIZE, SIZE),
+                                   input_kernel='rick_inc_input_raw_f32')
+                wpk = pack_fc_weight(fc[0])
+                if wpk.numel() != _lib.lib.rick_fc_packed_floats(POOL3, CLASSES):
+                    raise RuntimeError(f'InceptionV3Logits: packed fc weight has {wpk.numel()} floats, the kernel expects '
+                                       f'{_lib.lib.rick_fc_packed_floats(POOL3, CLASSES)}')
+                self._wpk, self._bias = wpk.to(self.device), fc[1].to(self.device)
+                self._pool3 = torch.empty(self.batch * POOL3, device=self.device, dtype=torch.float32)
+                rows = min(self.batch, FC_MAX_ROWS)
+                self._ws = torch.empty(_lib.lib.rick_fc_workspace_floats(rows, POOL3, CLASSES), device=self.device,
+                                       dtype=torch.float32)
+
+    @classmethod
+    def load(cls, src, device='cuda', batch=100, size=None):
+        """src: a path (torch.load, weights_only) or a state_dict, torchvision or reference-wrapper layout, with fc.weight and
+        fc.bias."""
+        if not isinstance(src, dict):
+            src = torch.load(src, map_location='cpu', weights_only=True)
+        return cls(fold(src, 3), fc_from_state_dict(src), device=device, batch=batch, size=size)
+
+    def _run_fc(self, lo, m, out):
+        """Rows [lo, lo + m) of the pool3 workspace (m <= 64) through the classifier -> the same rows of out."""
+        from . import _lib as lib
+        lib.check(lib.lib.rick_fc_f32(self._pool3.data_ptr() + 4 * lo * POOL3, self._wpk.data_ptr(), self._bias.data_ptr(),
+                                      self._ws.data_ptr(), out.data_ptr() + 4 * lo * CLASSES, m, POOL3, CLASSES, 0,
+                                      lib.stream_ptr()), 'rick_fc_f32')
+
+    def _run(self, x, out):
+        """x [n, 3, H, W] contiguous (n <= batch) -> out [n, 1000]: the trunk, pool3 into the workspace, fc in chunks of 64 rows."""
+        from .fc import FC_MAX_ROWS
+        n = x.shape[0]
+        self._plan.run(x, self._pool3)
+        for lo in range(0, n, FC_MAX_ROWS):
+            self._run_fc(lo, min(FC_MAX_ROWS, n - lo), out)
+
+    @torch.no_grad()
+    def __call__(self, images):
+        if images.dim() != 4 or images.shape[1] != 3:
+            raise RuntimeError(f'InceptionV3Logits: expected images [N, 3, H, W], got {tuple(images.shape)}')
+        if images.dtype != torch.float32:
+            raise RuntimeError(f'InceptionV3Logits: images must be float32, got {images.dtype}')
+        if self.size is not None and tuple(images.shape[2:]) != self.size:
+            raise RuntimeError(f'InceptionV3Logits: loaded for images of {self.size}, got {tuple(images.shape[2:])}')
+        if images.device.type == 'cpu':
+            out = torch.empty((images.shape[0], CLASSES), dtype=torch.float32)
+            for lo in range(0, images.shape[0], self.batch):
+                x = images[lo:lo + self.batch]
+                if self.size is None:
+                    x = F.interpolate(x, (SIZE, SIZE), mode='bilinear', align_corners=False)
+                out[lo:lo + self.batch] = F.linear(_cpu_forward(self.folded, x, 3, affine=False), *self.fc)
+            return out
+        if self._plan is None or images.device != self.device:
+            raise RuntimeError(f'InceptionV3Logits: images on {images.device}, network loaded for {self.device}')
+        x = images.detach().contiguous()
+        N = x.shape[0]
+        out = torch.empty((N, CLASSES), device=x.device, dtype=torch.float32)
+        with torch.cuda.device(self.device):
+            for lo in range(0, N, self.batch):
+                hi = min(N, lo + self.batch)
+                self._run(x[lo:hi], out[lo:hi])
+        return out
+
+    @torch.no_grad()
+    def probs(self, images):
+        """softmax(logits) [N, 1000] fp32: rick_is_rows_f32 on the device, F.softmax on CPU tensors."""
+        logits = self(images)
+        if logits.device.type == 'cpu':
+            return F.softmax(logits, dim=-1)
+        return softmax_rows(logits)[0]

@@ -30,12 +30,12 @@ torch composition.
 import torch
 import torch.nn.functional as F
 
+from .fc import FC_MAX_ROWS, pack_fc_weight  # noqa: F401  (pack_fc_weight is part of this module's surface)
 from .vgg_trunk import STAGES, VggTrunk, cpu_stages
 
 SIZE = 224
 POOLED = (7, 7, 512)            # (y, x, c) of the trunk's NHWC output after the fifth pool
 FC_IN, FEATURES = 7 * 7 * 512, 4096
-FC_MAX_ROWS = 64                # rick_fc_f32 takes 1 <= M <= 64 rows per call
 
 
 # ---- loading --------------------------------------------------------------------------------------------------------------
@@ -72,16 +72,6 @@ def permute_fc1(w):
     """fc1 weight [4096, 25088] with K in the reference's (c, y, x) flatten order -> K in the trunk's NHWC (y, x, c) order."""
     y, x, c = POOLED
     return w.view(w.shape[0], c, y, x).permute(0, 2, 3, 1).reshape(w.shape[0], FC_IN).contiguous()
-
-
-def pack_fc_weight(w):
-    """W [N, K] fp32 -> the layout rick_fc_f32 streams (include/rick_hip.h): [Np / 32][Kp / 8][64 lanes][4], zero padded to
-    Np = N rounded up to 128 and Kp = K rounded up to 8; lane (h = lane >> 5, c = lane & 31) of column block nb and k block kb
-    holds W[32 nb + c][8 kb + 2 j + h] in component j."""
-    n, k = w.shape
-    np_, kp = -(-n // 128) * 128, -(-k // 8) * 8
-    wp = F.pad(w, (0, kp - k, 0, np_ - n))
-    return wp.view(np_ // 32, 32, kp // 8, 4, 2).permute(0, 2, 4, 1, 3).contiguous().view(-1)       # (nb, kb, h, c, j)
 
 
 def _load_dict(src):

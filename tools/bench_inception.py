@@ -3,6 +3,10 @@ torch fp32 composition (F.conv2d ... on the same device), and the wall time of a
 (Evaluator.compute_inception_score) split into G sampling, features and statistics.  Seeded random weights (timing only).
 
   python tools/bench_inception.py [--iters 10] [--nsamples 5000] [--size 256]
+  python tools/bench_inception.py --score [--iters 10] [--nsamples 5000] [--size 256]
+--score: the Inception Score path instead (InceptionV3Logits, rick_amd.evaluate.InceptionScoreStats): img/s of the logits
+network at the native size and resized to 299, the head's share of it (fc + softmax rows + accumulation), and the wall time of
+a 5 000-sample Evaluator.compute_inception_score(iscore=True).
 Prints a readable report and one JSON line."""
 import argparse
 import json
@@ -66,13 +70,81 @@ def timed(fn, iters):
     return e0.elapsed_time(e1) / 1e3 / iters
 
 
+def score_mode(args):
+    """Throughput of the Inception Score path and the wall time of an evaluation with iscore=True."""
+    from rick_amd.evaluate import Evaluator, InceptionScoreStats
+    from rick_amd.inception import CLASSES, POOL3, InceptionV3Logits, accumulate_rows, softmax_rows
+    dev = 'cuda'
+    sd = seeded_state_dict()
+    g = torch.Generator().manual_seed(1)
+    sd['fc.weight'], sd['fc.bias'] = torch.randn(CLASSES, POOL3, generator=g) * 0.05, torch.randn(CLASSES, generator=g) * 0.1
+    res = {'metric': 'inception_score', 'size': args.size}
+    nets = {'native': InceptionV3Logits.load(sd, device=dev, batch=100, size=(args.size, args.size)),
+            'resize299': InceptionV3Logits.load(sd, device=dev, batch=100, size=None)}
+    for tag, net in nets.items():
+        for n in (25, 100):
+            x = torch.rand(n, 3, args.size, args.size, device=dev, generator=torch.Generator(dev).manual_seed(n)) * 2 - 1
+            st = InceptionScoreStats(net, 1 << 40, 1)
+            logits = net(x)
+            acc = torch.zeros(1, 2 * CLASSES + 1, device=dev, dtype=torch.float64)
+
+            def head():
+                for lo in range(0, n, 64):
+                    net._run_fc(lo, min(64, n - lo), logits)
+                p, s_, h = softmax_rows(logits)
+                accumulate_rows(acc, p, s_, h, 0, 1 << 40)
+            t_net = timed(lambda: net(x), args.iters)
+            t_all = timed(lambda: st.update(x), args.iters)
+            t_head = timed(head, args.iters * 5)
+            res[f'{tag}_logits_img_s_n{n}'] = n / t_net
+            res[f'{tag}_update_img_s_n{n}'] = n / t_all
+            res[f'{tag}_head_share_n{n}'] = t_head / t_all
+            print(f'{tag:9s} {args.size}^2 N={n:4d}: logits {n / t_net:8.1f} img/s   update (logits + rows + accumulate) '
+                  f'{n / t_all:8.1f} img/s   head (fc + rows + accumulate) {t_head * 1e6:7.1f} us = {100 * t_head / t_all:.2f} % of '
+                  f'an update', flush=True)
+    if not args.skip_eval:
+        from rick_amd.models import Generator
+        from rick_amd.synth import synth_state_dict
+        from tests.shapes import generator_shapes
+        gen = Generator(args.size, 512, 8, channel_multiplier=2)
+        gen.load_state_dict(synth_state_dict(generator_shapes(args.size)), strict=False)
+        gen = gen.to(dev)
+        ns = args.nsamples
+        feature_fn = lambda img: img.mean((2, 3))                                 # noqa: E731  (FID is not what is timed here)
+        real = torch.randn(ns, 3, device=dev)
+        for tag, net in nets.items():
+            ev = Evaluator(gen, feature_fn, real, n_sample_store=25, inception_nsamples=100, fid_sample_size=100, is_net=net)
+            ev.compute_inception_score(fid=False, iscore=True)                    # warm-up (allocator, kernels)
+            ev.inception_nsamples = ev.sample_size = ns
+            times = {}
+            for iscore in (False, True):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                score = ev.compute_inception_score(fid=False, iscore=iscore, is_splits=10)
+                if iscore:
+                    float(score['is'])
+                torch.cuda.synchronize()
+                times[iscore] = time.perf_counter() - t0
+            res[f'eval_{tag}_s'], res[f'eval_{tag}_sampling_only_s'] = times[True], times[False]
+            print(f'Evaluator.compute_inception_score(fid=False, iscore=True, is_splits=10), {ns} images at {args.size}^2, '
+                  f'{tag}: {times[True]:.2f} s (the same loop without the score: {times[False]:.2f} s)', flush=True)
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--iters', type=int, default=10)
     ap.add_argument('--nsamples', type=int, default=5000)
     ap.add_argument('--size', type=int, default=256)
     ap.add_argument('--skip-eval', action='store_true')
+    ap.add_argument('--score', action='store_true', help='the Inception Score path instead of the FID features')
     args = ap.parse_args()
+    if args.score:
+        torch.backends.cudnn.allow_tf32 = False
+        torch.backends.cuda.matmul.allow_tf32 = False
+        with torch.no_grad():
+            score_mode(args)
+        return
     from rick_amd.inception import InceptionV3Features, _cpu_forward, fold
     torch.backends.cudnn.allow_tf32 = False
     torch.backends.cuda.matmul.allow_tf32 = False
