@@ -570,6 +570,15 @@ int rick_augment_adj_f32(const float *gy, const rick_aug_param *params, float *w
  *   Cop = Co rounded up to bn (64 or 128), zero-padded; bias [Cop].  Output columns [seg_start[s], seg_start[s+1]) go to
  *   dst[s] + pixel * ldc[s] + c0[s] (a channel slice of a wider NHWC tensor: concats are free); seg_start[0] = 0, unused
  *   slots >= Co.  Columns of one GEMM that read the same input (the fused 1x1 heads) are routed this way.
+ * rick_inc_conv_bwd_f32: the data gradient of a 3x3 stride-1 pad-1 convolution, the same implicit GEMM with another epilogue
+ *   (rick_inc_conv_f32's kernels are unchanged): gout [N, H, W, Ci] is the gradient of the forward convolution's output (Ci =
+ *   its output channels, Ci % 4 == 0), Co its input channels; wt [Kp][Cop] is the transposed, 180-degree rotated filter packed
+ *   once, wt[(ky, kx, co_f)][ci_f] = W[co_f][ci_f][2 - ky][2 - kx], padded like wpk.  a: KH = KW = 3, SH = SW = PH = PW = 1,
+ *   OH = IH, OW = IW, nseg = 1, c0[0] = 0, ldc[0] = Co.  No bias, no ReLU:
+ *   dst[0][p, c] = (mask[p, c] > 0) ? acc + add[p, c] : 0, with mask the stored forward activation the gradient is taken with
+ *   respect to (torch's ReLU rule, out > 0) and add a gradient that reaches that activation by another way (a tap); both
+ *   [M, Co] like the output, either may be NULL (no mask / nothing added).  No split-K: an image's gradient is bit-identical
+ *   whatever batch it is computed in.
  * rick_inc_maxpool_f32: 3x3 stride 2 max, no padding, [N, IH, IW, C] -> channels [c0, c0 + C) of an ldc-wide output.
  * rick_inc_avgpool_f32: 3x3 stride 1 pad 1 average with count_include_pad, [N, H, W, C] -> same shape.
  * rick_inc_mean_f32: [N, HW, C] -> [N, C] mean over HW in pixel order.
@@ -594,6 +603,8 @@ typedef struct {
 } rick_inc_conv;
 int rick_inc_input_f32(const float *x, float *out, int N, int H, int W, int OH, int OW, void *stream);
 int rick_inc_conv_f32(const float *in, const float *wpk, const float *bias, const rick_inc_conv *a, void *stream);
+int rick_inc_conv_bwd_f32(const float *gout, const float *wt, const float *mask, const float *add, const rick_inc_conv *a,
+                          void *stream);
 int rick_inc_maxpool_f32(const float *in, float *out, int N, int IH, int IW, int C, int ldc, int c0, void *stream);
 int rick_inc_avgpool_f32(const float *in, float *out, int N, int H, int W, int C, void *stream);
 int rick_inc_mean_f32(const float *in, float *out, int N, int HW, int C, void *stream);
@@ -617,6 +628,20 @@ int rick_is_accum_f64(const float *p, const double *s, const double *h, double *
  *   only: d(x, x) = 0 and D(A, B) = D(B, A)^T exactly, and a pair's value does not depend on the other images of the call.
  * rick_lpips_reduce_f32: part = the nlayers taps' partials one after the other ([nslices[l]][na][nb] each) -> out [na, nb]
  *   fp32 = sum over taps in order of (sum over slices in order) / hw[l], in fp64.
+ * The backward pass of the paired distance (rick_amd/lpips.py: LPIPS.loss), first order, with respect to the image:
+ * rick_lpips_tap_bwd_f32: one tap.  a [n, HW, C] with inverse norms ia [n, HW] (the image), t / it the target's, of nt = n
+ *   images or nt = 1 image broadcast, lin weights w [C] (C % 4 == 0, C <= 1024), upstream gradient go [n] ->
+ *   g [n, HW, C] = d/da of go (1 / HW) sum_p sum_c w_c (a_c ia - t_c it)^2: with u = a ia, r_c = 2 w_c (u_c - t_c it) go / HW
+ *   and |a| = 1 / ia - 1e-10, g_k = ia r_k - a_k (sum_c r_c a_c) ia^2 / |a|; exactly 0 where ia = 0, and exactly 0 where the
+ *   image equals the target.  One wave per position: lane l sums channels 4 l + 256 j (j ascending), then the wave_sum
+ *   butterfly.  relu != 0 also applies the ReLU rule g = (a > 0) ? g : 0 (the gradient in front of the tap's ReLU).
+ * rick_lpips_maxpool2_bwd_f32: the adjoint of rick_lpips_maxpool2_f32 in gather form, fused with the stage output's tap
+ *   gradient and ReLU mask.  act [N, IH, IW, C] is the pooled activation, gpool [N, IH / 2, IW / 2, C] the gradient of the pool's
+ *   output, add [N, IH, IW, C] (may be NULL) the tap gradient:
+ *   out[p] = (act[p] > 0) ? add[p] + (p is the first maximum of its window in (dy, dx) scan order ? gpool[window] : 0) : 0.
+ *   Positions that the floor leaves outside every window receive only add.
+ * rick_lpips_input_bwd_f32: the adjoint of rick_lpips_input_f32, mode 0: g [N, H, W, 4] -> out [N, 3, H, W] planar,
+ *   out = g_c / scale_c (one correctly rounded fp32 division).
  * No atomics: every output element has one writer and a fixed summation order. */
 typedef struct {
     int nlayers;
@@ -629,6 +654,11 @@ int rick_lpips_invnorm_f32(const float *in, float *out, int64_t P, int C, void *
 int rick_lpips_pair_f32(const float *fa, const float *ia, int na, const float *fb, const float *ib, int nb, const float *w,
                         int HW, int C, int pps, double *part, void *stream);
 int rick_lpips_reduce_f32(const double *part, float *out, int na, int nb, const rick_lpips_layers *d, void *stream);
+int rick_lpips_tap_bwd_f32(const float *a, const float *ia, const float *t, const float *it, int n, int nt, const float *w,
+                           const float *go, int HW, int C, int relu, float *g, void *stream);
+int rick_lpips_maxpool2_bwd_f32(const float *act, const float *add, const float *gpool, float *out, int N, int IH, int IW, int C,
+                                void *stream);
+int rick_lpips_input_bwd_f32(const float *g, float *out, int N, int H, int W, void *stream);
 
 /* ---------------------------------------------------------------------------------------
  * VGG16 fc2 — the features behind the reference's improved precision / recall (rick_amd/vgg.py;

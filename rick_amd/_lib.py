@@ -172,6 +172,7 @@ SIGNATURES = {
     'rick_augment_adj_f32': (c_int, [c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_fp]),
     'rick_inc_input_f32': (c_int, [c_fp, c_fp, c_int, c_int, c_int, c_int, c_int, c_fp]),
     'rick_inc_conv_f32': (c_int, [c_fp, c_fp, c_fp, ctypes.POINTER(IncConv), c_fp]),
+    'rick_inc_conv_bwd_f32': (c_int, [c_fp, c_fp, c_fp, c_fp, ctypes.POINTER(IncConv), c_fp]),
     'rick_inc_maxpool_f32': (c_int, [c_fp, c_fp, c_int, c_int, c_int, c_int, c_int, c_int, c_fp]),
     'rick_inc_avgpool_f32': (c_int, [c_fp, c_fp, c_int, c_int, c_int, c_int, c_fp]),
     'rick_inc_mean_f32': (c_int, [c_fp, c_fp, c_int, c_int, c_int, c_fp]),
@@ -183,6 +184,9 @@ SIGNATURES = {
     'rick_lpips_invnorm_f32': (c_int, [c_fp, c_fp, c_i64, c_int, c_fp]),
     'rick_lpips_pair_f32': (c_int, [c_fp, c_fp, c_int, c_fp, c_fp, c_int, c_fp, c_int, c_int, c_int, c_fp, c_fp]),
     'rick_lpips_reduce_f32': (c_int, [c_fp, c_fp, c_int, c_int, ctypes.POINTER(LpipsLayers), c_fp]),
+    'rick_lpips_tap_bwd_f32': (c_int, [c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_fp, c_fp, c_int, c_int, c_int, c_fp, c_fp]),
+    'rick_lpips_maxpool2_bwd_f32': (c_int, [c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, c_fp]),
+    'rick_lpips_input_bwd_f32': (c_int, [c_fp, c_fp, c_int, c_int, c_int, c_fp]),
     'rick_vgg_input_f32': (c_int, [c_fp, c_fp, c_int, c_int, c_int, c_fp]),
     'rick_fc_packed_floats': (c_i64, [c_int, c_int]),
     'rick_fc_workspace_floats': (c_i64, [c_int, c_int, c_int]),

@@ -64,9 +64,12 @@ template <int BN>
 __device__ __forceinline__ float4 inc_ld_b(const float *wpk, int k0, int idx, int Cop, int n0) {   // item idx of the [32][BN] tile
     return *reinterpret_cast<const float4 *>(wpk + (int64_t)(k0 + idx / (BN / 4)) * Cop + n0 + 4 * (idx % (BN / 4)));
 }
-template <int NT>
+// BWD = true is the data gradient of a 3x3 stride-1 pad-1 convolution (rick_inc_conv_bwd_f32): the same GEMM over the
+// transposed, rotated filter with the epilogue out = (mask > 0) ? acc + add : 0 in place of bias + ReLU; one destination.
+template <int NT, bool BWD = false>
 __global__ __launch_bounds__(256) void inc_conv_kernel(const float *__restrict__ in, const float *__restrict__ wpk,
-                                                       const float *__restrict__ bias, rick_inc_conv a) {
+                                                       const float *__restrict__ bias, rick_inc_conv a,
+                                                       const float *__restrict__ mask, const float *__restrict__ add) {
     constexpr int BN = 64 * NT;
     __shared__ float As[IC_BK * IC_AS];
     __shared__ __attribute__((aligned(16))) float Bs[IC_BK * BN];
@@ -147,6 +150,21 @@ __global__ __launch_bounds__(256) void inc_conv_kernel(const float *__restrict__
     for (int j = 0; j < NT; j++) {
         const int col = n0 + wn * 32 * NT + 32 * j + l32;
         if (col >= a.Co) continue;
+        if constexpr (BWD) {
+#pragma unroll
+            for (int i = 0; i < 2; i++)
+#pragma unroll
+                for (int e = 0; e < 16; e++) {
+                    const int m = m0 + wm * 64 + 32 * i + (e & 3) + 8 * (e >> 2) + 4 * h;
+                    if (m >= M) continue;
+                    const int64_t o = (int64_t)m * a.ldc[0] + col;
+                    float v = acc[i][j][e];
+                    if (add) v += add[o];
+                    if (mask) v = mask[o] > 0.f ? v : 0.f;
+                    a.dst[0][o] = v;
+                }
+            continue;
+        }
         const int sg = (col >= a.seg_start[1]) + (col >= a.seg_start[2]) + (col >= a.seg_start[3]);
         float *dst;
         int ldc;
@@ -339,9 +357,32 @@ extern "C" int rick_inc_conv_f32(const float *in, const float *wpk, const float 
     if (M > 0x7fffffff || (int64_t)g.N * g.IH * g.IW * g.Ci > ((int64_t)1 << 40)) return RICK_EINVAL;
     const dim3 grid((unsigned)cdiv64(M, IC_BM), (unsigned)(g.Cop / g.bn));
     if (g.bn == 128)
-        hipLaunchKernelGGL(inc_conv_kernel<2>, grid, dim3(256), 0, (hipStream_t)stream, in, wpk, bias, g);
+        hipLaunchKernelGGL(inc_conv_kernel<2>, grid, dim3(256), 0, (hipStream_t)stream, in, wpk, bias, g, nullptr, nullptr);
     else
-        hipLaunchKernelGGL(inc_conv_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, in, wpk, bias, g);
+        hipLaunchKernelGGL(inc_conv_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, in, wpk, bias, g, nullptr, nullptr);
+    RICK_LAUNCH_STATUS();
+}
+
+extern "C" int rick_inc_conv_bwd_f32(const float *gout, const float *wt, const float *mask, const float *add,
+                                     const rick_inc_conv *a, void *stream) {
+    if (!gout || !wt || !a) return RICK_EINVAL;
+    const rick_inc_conv g = *a;
+    if (g.N < 0 || g.IH <= 0 || g.IW <= 0 || g.Ci <= 0 || (g.Ci & 3) || g.KH != 3 || g.KW != 3 || g.SH != 1 || g.SW != 1 ||
+        g.PH != 1 || g.PW != 1 || g.OH != g.IH || g.OW != g.IW || g.Co <= 0 || g.nseg != 1 || (g.bn != 64 && g.bn != 128) ||
+        g.Cop % g.bn || g.Cop < g.Co)
+        return RICK_EINVAL;
+    if (g.seg_start[0] != 0 || g.seg_start[1] < g.Co || g.seg_start[2] < g.Co || g.seg_start[3] < g.Co || !g.dst[0] ||
+        g.c0[0] != 0 || g.ldc[0] != g.Co)
+        return RICK_EINVAL;                  // mask and add share the output's [M, Co] layout
+    if (((uintptr_t)gout | (uintptr_t)wt) % 16) return RICK_EINVAL;
+    if (g.N == 0) return 0;
+    const int64_t M = (int64_t)g.N * g.OH * g.OW;
+    if (M > 0x7fffffff || (int64_t)g.N * g.IH * g.IW * g.Ci > ((int64_t)1 << 40)) return RICK_EINVAL;
+    const dim3 grid((unsigned)cdiv64(M, IC_BM), (unsigned)(g.Cop / g.bn));
+    if (g.bn == 128)
+        hipLaunchKernelGGL((inc_conv_kernel<2, true>), grid, dim3(256), 0, (hipStream_t)stream, gout, wt, nullptr, g, mask, add);
+    else
+        hipLaunchKernelGGL((inc_conv_kernel<1, true>), grid, dim3(256), 0, (hipStream_t)stream, gout, wt, nullptr, g, mask, add);
     RICK_LAUNCH_STATUS();
 }
 

@@ -170,6 +170,107 @@ __global__ __launch_bounds__(256) void lp_reduce_kernel(const double *__restrict
     out[q] = (float)tot;
 }
 
+// ---- backward of one tap's distance with respect to the image's features ------------------------------------------------------
+// g = d/da of go (1 / HW) sum_p sum_c w_c (a_c ia - t_c it)^2.  One wave per position; lane l owns channels 4 l + 256 j and adds
+// its r_c a_c in that order (fma chain), then the wave_sum butterfly.  The target is image n of nt == n images or the one image.
+__global__ __launch_bounds__(256) void lp_tap_bwd_kernel(const float *__restrict__ a, const float *__restrict__ ia,
+                                                         const float *__restrict__ t, const float *__restrict__ it, int nt,
+                                                         const float *__restrict__ w, const float *__restrict__ go, int HW, int C,
+                                                         int relu, float *__restrict__ g, int64_t P) {
+    const int lane = threadIdx.x & 63;
+    const int64_t p = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (p >= P) return;                                                // wave-uniform
+    const int64_t n = p / HW, pt = nt == 1 ? p - n * HW : p;
+    const float *ar = a + p * C, *tr = t + pt * C;
+    float *gr = g + p * C;
+    const float sa = ia[p], st = it[pt];
+    if (!(sa > 0.f)) {                                                 // an all-zero position: the distance does not depend on it
+        for (int c = 4 * lane; c < C; c += 256) *reinterpret_cast<float4 *>(gr + c) = make_float4(0.f, 0.f, 0.f, 0.f);
+        return;
+    }
+    const float gs = __fdiv_rn(go[n], (float)HW);
+    float4 av[LP_MAXC / 256], rv[LP_MAXC / 256];
+    float s = 0.f;
+#pragma unroll
+    for (int j = 0; j < LP_MAXC / 256; j++) {
+        const int c = 4 * lane + 256 * j;
+        if (c >= C) break;
+        const float4 x = *reinterpret_cast<const float4 *>(ar + c), y = *reinterpret_cast<const float4 *>(tr + c);
+        const float4 wv = *reinterpret_cast<const float4 *>(w + c);
+        float4 r;
+        r.x = 2.f * wv.x * (x.x * sa - y.x * st) * gs;
+        r.y = 2.f * wv.y * (x.y * sa - y.y * st) * gs;
+        r.z = 2.f * wv.z * (x.z * sa - y.z * st) * gs;
+        r.w = 2.f * wv.w * (x.w * sa - y.w * st) * gs;
+        s = fmaf(r.x, x.x, s);
+        s = fmaf(r.y, x.y, s);
+        s = fmaf(r.z, x.z, s);
+        s = fmaf(r.w, x.w, s);
+        av[j] = x;
+        rv[j] = r;
+    }
+    s = wave_sum(s);
+    const float na = __fsub_rn(__fdiv_rn(1.f, sa), 1e-10f);            // |a|, undoing the epsilon of the inverse norm
+    const float q = na > 0.f ? __fdiv_rn(s * sa * sa, na) : 0.f;
+#pragma unroll
+    for (int j = 0; j < LP_MAXC / 256; j++) {
+        const int c = 4 * lane + 256 * j;
+        if (c >= C) break;
+        const float4 x = av[j], r = rv[j];
+        float4 o = make_float4(sa * r.x - x.x * q, sa * r.y - x.y * q, sa * r.z - x.z * q, sa * r.w - x.w * q);
+        if (relu) o = make_float4(x.x > 0.f ? o.x : 0.f, x.y > 0.f ? o.y : 0.f, x.z > 0.f ? o.z : 0.f, x.w > 0.f ? o.w : 0.f);
+        *reinterpret_cast<float4 *>(gr + c) = o;
+    }
+}
+
+// ---- 2x2 max-pool backward, gather form, fused with the tap gradient and the ReLU mask of the pooled activation ---------------
+// One thread per pre-pool position and 4 channels.  The window's maximum goes to its first position in (dy, dx) scan order
+// (torch's max_pool2d rule); positions the floor leaves outside every window only pass `add` on.
+__device__ __forceinline__ float lp_pool_pick(float v0, float v1, float v2, float v3, int k, float gp) {
+    const float m = fmaxf(fmaxf(v0, v1), fmaxf(v2, v3));
+    const int first = v0 == m ? 0 : v1 == m ? 1 : v2 == m ? 2 : 3;
+    return first == k ? gp : 0.f;
+}
+__global__ __launch_bounds__(256) void lp_maxpool2_bwd_kernel(const float *__restrict__ act, const float *__restrict__ add,
+                                                              const float *__restrict__ gpool, float *__restrict__ out, int N,
+                                                              int IH, int IW, int C) {
+    const int OH = IH / 2, OW = IW / 2, C4 = C / 4;
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (int64_t)N * IH * IW * C4) return;
+    const int c = (int)(i % C4) * 4;
+    const int64_t p = i / C4;
+    const int x = (int)(p % IW), y = (int)((p / IW) % IH);
+    const int64_t n = p / ((int64_t)IW * IH);
+    const float4 v = *reinterpret_cast<const float4 *>(act + p * C + c);
+    float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (add) o = *reinterpret_cast<const float4 *>(add + p * C + c);
+    const int oy = y >> 1, ox = x >> 1;
+    if (oy < OH && ox < OW) {
+        const float *b = act + ((n * IH + 2 * oy) * IW + 2 * ox) * C + c;
+        const float4 v0 = *reinterpret_cast<const float4 *>(b), v1 = *reinterpret_cast<const float4 *>(b + C);
+        const float4 v2 = *reinterpret_cast<const float4 *>(b + (int64_t)IW * C), v3 = *reinterpret_cast<const float4 *>(b + (int64_t)IW * C + C);
+        const float4 gp = *reinterpret_cast<const float4 *>(gpool + ((n * OH + oy) * OW + ox) * C + c);
+        const int k = 2 * (y & 1) + (x & 1);
+        o.x += lp_pool_pick(v0.x, v1.x, v2.x, v3.x, k, gp.x);
+        o.y += lp_pool_pick(v0.y, v1.y, v2.y, v3.y, k, gp.y);
+        o.z += lp_pool_pick(v0.z, v1.z, v2.z, v3.z, k, gp.z);
+        o.w += lp_pool_pick(v0.w, v1.w, v2.w, v3.w, k, gp.w);
+    }
+    reinterpret_cast<float4 *>(out)[i] = make_float4(v.x > 0.f ? o.x : 0.f, v.y > 0.f ? o.y : 0.f, v.z > 0.f ? o.z : 0.f,
+                                                     v.w > 0.f ? o.w : 0.f);
+}
+
+// ---- input backward (mode 0): NHWC4 gradient -> planar [N, 3, H, W], through the scaling layer's division ----------------------
+__global__ __launch_bounds__(256) void lp_input_bwd_kernel(const float *__restrict__ g, float *__restrict__ out, int N, int HW) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (int64_t)N * HW) return;
+    const int64_t n = i / HW, p = i - n * HW;
+    const float4 v = reinterpret_cast<const float4 *>(g)[i];
+    out[(n * 3 + 0) * HW + p] = __fdiv_rn(v.x, lp_scale[0]);
+    out[(n * 3 + 1) * HW + p] = __fdiv_rn(v.y, lp_scale[1]);
+    out[(n * 3 + 2) * HW + p] = __fdiv_rn(v.z, lp_scale[2]);
+}
+
 static unsigned lp_grid(int64_t n) { return (unsigned)((n + 255) / 256); }
 
 extern "C" int rick_lpips_input_f32(const float *x, const uint8_t *xq, float *out, uint8_t *u8out, int N, int H, int W,
@@ -216,5 +317,38 @@ extern "C" int rick_lpips_reduce_f32(const double *part, float *out, int na, int
         if (d->nslices[l] <= 0 || d->hw[l] <= 0) return RICK_EINVAL;
     if (na == 0 || nb == 0) return 0;
     hipLaunchKernelGGL(lp_reduce_kernel, dim3(lp_grid((int64_t)na * nb)), dim3(256), 0, (hipStream_t)stream, part, out, na, nb, *d);
+    RICK_LAUNCH_STATUS();
+}
+
+extern "C" int rick_lpips_tap_bwd_f32(const float *a, const float *ia, const float *t, const float *it, int n, int nt,
+                                      const float *w, const float *go, int HW, int C, int relu, float *g, void *stream) {
+    if (!a || !ia || !t || !it || !w || !go || !g || n < 0 || (nt != n && nt != 1) || HW <= 0 || C <= 0 || (C & 3) || C > LP_MAXC)
+        return RICK_EINVAL;
+    if (((uintptr_t)a | (uintptr_t)t | (uintptr_t)w | (uintptr_t)g) % 16) return RICK_EINVAL;
+    if (n == 0) return 0;
+    const int64_t P = (int64_t)n * HW;
+    if (cdiv64(P, 4) > 0x7fffffff) return RICK_EINVAL;
+    hipLaunchKernelGGL(lp_tap_bwd_kernel, dim3((unsigned)cdiv64(P, 4)), dim3(256), 0, (hipStream_t)stream, a, ia, t, it, nt, w, go,
+                       HW, C, relu, g, P);
+    RICK_LAUNCH_STATUS();
+}
+
+extern "C" int rick_lpips_maxpool2_bwd_f32(const float *act, const float *add, const float *gpool, float *out, int N, int IH,
+                                           int IW, int C, void *stream) {
+    if (!act || !gpool || !out || N < 0 || IH < 2 || IW < 2 || C <= 0 || (C & 3)) return RICK_EINVAL;
+    if (((uintptr_t)act | (uintptr_t)add | (uintptr_t)gpool | (uintptr_t)out) % 16) return RICK_EINVAL;
+    if (N == 0) return 0;
+    const int64_t total = (int64_t)N * IH * IW * (C / 4);
+    if (cdiv64(total, 256) > 0x7fffffff) return RICK_EINVAL;
+    hipLaunchKernelGGL(lp_maxpool2_bwd_kernel, dim3(lp_grid(total)), dim3(256), 0, (hipStream_t)stream, act, add, gpool, out, N,
+                       IH, IW, C);
+    RICK_LAUNCH_STATUS();
+}
+
+extern "C" int rick_lpips_input_bwd_f32(const float *g, float *out, int N, int H, int W, void *stream) {
+    if (!g || !out || N < 0 || H <= 0 || W <= 0 || ((uintptr_t)g % 16)) return RICK_EINVAL;
+    if (N == 0) return 0;
+    if (cdiv64((int64_t)N * H * W, 256) > 0x7fffffff) return RICK_EINVAL;
+    hipLaunchKernelGGL(lp_input_bwd_kernel, dim3(lp_grid((int64_t)N * H * W)), dim3(256), 0, (hipStream_t)stream, g, out, N, H * W);
     RICK_LAUNCH_STATUS();
 }

@@ -25,6 +25,13 @@ no split-K: an image's taps are bit-identical whatever batch it is computed in).
 activation buffers and one tap set of ``batch`` images at ``size`` x ``size``) is allocated once in ``load``.  CPU tensors
 run the same network as a plain fp32 torch composition.
 
+``net.loss(x, target)`` is the same paired distance as a loss: differentiable (first order) with respect to the image x,
+against a fixed target (an image tensor, or the LpipsFeatures of N images or of one image for all).  On the device the forward
+run keeps the 13 activations of the trunk in a workspace of ``batch`` images at ``size`` x ``size`` that is allocated on the
+first differentiable call, and the backward pass runs on rick_lpips_tap_bwd_f32 (the distance), rick_inc_conv_bwd_f32 (the
+convolutions' data gradients, the transposed filters packed at load), rick_lpips_maxpool2_bwd_f32 (pool adjoint + tap gradient
++ ReLU mask) and rick_lpips_input_bwd_f32.  The weights are constants; the no-grad entries launch what they always did.
+
 ``src`` is a path to (or the contents of) either ``lpips.LPIPS(net='vgg').state_dict()`` (``net.slice{1..5}.{idx}.*``,
 ``lin{k}.model.1.weight``, optionally the ``lins.{k}.*`` duplicates and the ``scaling_layer.*`` buffers), or use
 ``LPIPS.load(vgg=..., lin=...)`` with a torchvision ``vgg16`` state_dict (``features.{idx}.*``; ``classifier.*`` ignored)
@@ -196,13 +203,14 @@ class _Plan:
         from . import _lib
         self._lib = _lib
         self.batch, self.size, self.pixels = batch, size, batch * size * size
-        self.trunk = VggTrunk(convs, device)
+        self.trunk = VggTrunk(convs, device, transposed=True)
         self.x0 = torch.empty(self.pixels * 4, device=device, dtype=torch.float32)
         self.bufs = self.trunk.new_buffers(self.pixels, device)
         self.lins = [w.to(device) for w in lins]
 
-    def run(self, x, mode, out, u8out):
-        """x [n, 3, H, W] (fp32, or uint8 for mode 2), n * H * W <= pixels -> the taps of out (an LpipsFeatures of n)."""
+    def run(self, x, mode, out, u8out, keep=None):
+        """x [n, 3, H, W] (fp32, or uint8 for mode 2), n * H * W <= pixels -> the taps of out (an LpipsFeatures of n); keep:
+        VggTrunk.run's."""
         lib = self._lib
         n, _, H, W = x.shape
         stream = lib.stream_ptr()
@@ -213,7 +221,82 @@ class _Plan:
         def invnorm(s, tap, n, h, w):
             lib.check(lib.lib.rick_lpips_invnorm_f32(tap, out.inorm[s].data_ptr(), n * h * w, CHANNELS[s], stream),
                       'rick_lpips_invnorm_f32')
-        self.trunk.run(self.x0.data_ptr(), n, H, W, self.bufs, lambda s: out.taps[s].data_ptr(), invnorm)
+        self.trunk.run(self.x0.data_ptr(), n, H, W, self.bufs, lambda s: out.taps[s].data_ptr(), invnorm, keep=keep)
+
+
+class _GradWorkspace:
+    """What a differentiable call keeps between its forward and its backward run: the 13 activations of the trunk (the five
+    stage outputs as an LpipsFeatures with their inverse norms) and three gradient buffers, for `batch` images at size x size
+    (any n * H * W up to that).  `version` counts forward runs: a backward run whose activations were overwritten refuses."""
+
+    def __init__(self, plan, device):
+        f32 = dict(device=device, dtype=torch.float32)
+        self.plan, self.pixels, self.version = plan, plan.pixels, 0
+        self.acts, area = [], 1.0
+        for s, stage in enumerate(STAGES):
+            area = area / 4 if s else area
+            self.acts += [torch.empty(int(self.pixels * area * co), **f32) for _, _, co in stage]
+        self.inorm = [torch.empty(max(1, self.pixels >> (2 * s)), **f32) for s in range(5)]
+        self.gbufs = [torch.empty(self.pixels * 64, **f32) for _ in range(3)]
+        self.last = [sum(len(st) for st in STAGES[:s + 1]) - 1 for s in range(5)]
+
+    def features(self, n, h, w):
+        """The stage outputs of n images of h x w as views of the workspace."""
+        taps = [self.acts[k][:n * a * b * c].view(n, a, b, c) for k, (a, b), c in zip(self.last, _tap_hw(h, w), CHANNELS)]
+        return LpipsFeatures(taps, [t[:n * a * b].view(n, a * b) for t, (a, b) in zip(self.inorm, _tap_hw(h, w))])
+
+    def forward(self, x):
+        n, _, H, W = x.shape
+        f = self.features(n, H, W)
+        self.version += 1
+        self.plan.run(x, 0, f, None, keep=[t.data_ptr() for t in self.acts])
+        return f
+
+    def backward(self, f, target, go, lins, gx):
+        """f: this workspace's features of the forward run; go [n] -> gx [n, 3, H, W]."""
+        lib = self.plan._lib
+        n, (H, W) = f.n, f.size
+        stream = lib.stream_ptr()
+
+        def tap_grad(s, ptr, n, h, w, relu):
+            lib.check(lib.lib.rick_lpips_tap_bwd_f32(f.taps[s].data_ptr(), f.inorm[s].data_ptr(), target.taps[s].data_ptr(),
+                                                     target.inorm[s].data_ptr(), n, target.n, lins[s].data_ptr(),
+                                                     go.data_ptr(), h * w, CHANNELS[s], int(relu), ptr, stream),
+                      'rick_lpips_tap_bwd_f32')
+        g0 = self.plan.trunk.run_backward(n, H, W, [t.data_ptr() for t in self.acts], self.gbufs, tap_grad)
+        lib.check(lib.lib.rick_lpips_input_bwd_f32(g0, gx.data_ptr(), n, H, W, stream), 'rick_lpips_input_bwd_f32')
+
+
+class _LpipsLoss(torch.autograd.Function):
+    """[N] paired LPIPS of x against fixed target features; the gradient with respect to x on the HIP backward kernels."""
+
+    @staticmethod
+    def forward(ctx, x, net, target):
+        ws = net._grad_workspace()
+        with torch.cuda.device(net.device):
+            f = ws.forward(x)
+            # n x n pairs for n values, as __call__ does: the pair kernel's 25 x 25 at 256^2 is about 2 ms next to the
+            # trunk's ~30 ms, and one launch per tap is cheaper than n launches of one pair each
+            d = net.distances(f, target)
+        ctx.net, ctx.target, ctx.f, ctx.version = net, target, f, ws.version
+        return torch.diagonal(d).contiguous() if target.n == f.n and f.n > 1 else d[:, 0].contiguous()
+
+    @staticmethod
+    def backward(ctx, go):
+        if torch.is_grad_enabled():
+            raise RuntimeError('LPIPS.loss: the backward pass is first order only (create_graph=True is not supported)')
+        ws = ctx.net._grad_workspace()
+        if ws.version != ctx.version:
+            raise RuntimeError('LPIPS.loss: the stored activations were overwritten by a later differentiable call; '
+                               'run backward before the next LPIPS.loss on this network')
+        if go.device != ctx.net.device or go.dtype != torch.float32:
+            raise RuntimeError(f'LPIPS.loss: upstream gradient on {go.device} / {go.dtype}')
+        n, (H, W) = ctx.f.n, ctx.f.size
+        go = go.contiguous()
+        gx = torch.empty((n, 3, H, W), device=go.device, dtype=torch.float32)
+        with torch.cuda.device(ctx.net.device):
+            ws.backward(ctx.f, ctx.target, go, ctx.net._plan.lins, gx)
+        return gx, None, None
 
 
 class LPIPS:
@@ -225,7 +308,7 @@ class LPIPS:
         self.convs, self.lins = convs, lins
         self.batch, self.size = int(batch), int(size)
         self.device = torch.device(device)
-        self._plan, self.workspace_features, self._second = None, None, None
+        self._plan, self.workspace_features, self._second, self._grad_ws = None, None, None, None
         if self.device.type == 'cuda':
             if self.device.index is None:
                 self.device = torch.device('cuda', torch.cuda.current_device())
@@ -336,6 +419,50 @@ class LPIPS:
     def _lib():
         from . import _lib
         return _lib
+
+    def _grad_workspace(self):
+        if self._grad_ws is None:
+            with torch.cuda.device(self.device):
+                self._grad_ws = _GradWorkspace(self._plan, self.device)
+        return self._grad_ws
+
+    def loss(self, x, target, quantize=False):
+        """Paired LPIPS as a loss: x [N, 3, H, W] fp32 (may require grad) against ``target``, an LpipsFeatures of N images
+        or of 1 image (compared with every x), or an image tensor of N or 1 images (its features are taken without a
+        gradient) -> [N] fp32, bit-identical to ``net(x, y)``.  Differentiable with respect to x only, first order only:
+        ``create_graph=True`` raises in the backward pass.  ``quantize`` (the PNG round trip) has no gradient: with an x that
+        requires one it raises.  On the device a differentiable call takes N * H * W <= batch * size^2, and its backward
+        pass must run before the next differentiable call on this network (one set of stored activations)."""
+        self._check_images(x, 'x')
+        if x.dtype != torch.float32:
+            raise RuntimeError(f'LPIPS.loss: x must be float32, got {x.dtype}')
+        needs_grad = torch.is_grad_enabled() and x.requires_grad
+        if quantize and needs_grad:
+            raise RuntimeError('LPIPS.loss: quantize=True rounds x to uint8 and has no gradient; pass quantize=False')
+        if torch.is_tensor(target):
+            target = self.features(target.detach(), quantize)
+        N, _, H, W = x.shape
+        if target.n not in (N, 1) or target.size != (H, W) or target.device != x.device:
+            raise RuntimeError(f'LPIPS.loss: target holds {target.n} images of {target.size} on {target.device}, x is '
+                               f'{N} of {(H, W)} on {x.device}')
+        if x.device.type == 'cpu':
+            xs, _ = scale_input(x, quantize)
+            val = 0
+            for s, fx in enumerate(_cpu_taps(self.convs, xs)):
+                ss = fx.pow(2).sum(1, keepdim=True)            # an all-zero position: 0 and gradient 0, as on the device
+                nx = torch.where(ss > 0, fx / (torch.where(ss > 0, ss, torch.ones_like(ss)).sqrt() + EPS), torch.zeros_like(fx))
+                ny = (target.taps[s] * target.inorm[s].view(target.taps[s].shape[:3])[..., None]).permute(0, 3, 1, 2)
+                val = val + ((nx - ny) ** 2 * self.lins[s].view(1, -1, 1, 1)).sum(1).mean((1, 2))
+            return val
+        if not needs_grad:
+            d = self.distances(self.features(x, quantize), target)
+            return torch.diagonal(d).contiguous() if target.n == N and N > 1 else d[:, 0].contiguous()
+        if N * H * W > self._plan.pixels:
+            raise ValueError(f'LPIPS.loss: {N} images of {H} x {W} exceed the workspace planned for {self.batch} x '
+                             f'{self.size}^2')
+        if not all(t.is_contiguous() for t in target.taps + target.inorm):
+            raise RuntimeError('LPIPS.loss: target feature tensors must be contiguous')
+        return _LpipsLoss.apply(x.contiguous(), self, target)
 
     @torch.no_grad()
     def __call__(self, x, y, quantize=False):

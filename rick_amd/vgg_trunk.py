@@ -3,7 +3,11 @@
 
 13 3x3 stride-1 pad-1 convolutions + ReLU on rick_inc_conv_f32 (f32-input MFMA, no split-K: an image's activations are
 bit-identical whatever batch it is computed in), a 2x2 stride-2 max pool (rick_lpips_maxpool2_f32) in front of every stage
-but the first.  Activations are NHWC fp32; the input is NHWC4 (channel 3 = 0)."""
+but the first.  Activations are NHWC fp32; the input is NHWC4 (channel 3 = 0).
+
+With ``transposed=True`` the trunk also holds every filter packed transposed and rotated, and ``run_backward`` carries a
+gradient from the five stage outputs back to the NHWC4 input on rick_inc_conv_bwd_f32 and rick_lpips_maxpool2_bwd_f32 (data
+gradients only: the weights are constants)."""
 import ctypes
 
 import torch
@@ -46,13 +50,25 @@ def pingpong_need():
     return need
 
 
+def pack_transposed(w):
+    """w [Co, Ci, 3, 3] -> the data gradient's GEMM operand [Kp, Cop]: Wt[(ky, kx, co)][ci] = W[co][ci][2 - ky][2 - kx], K =
+    9 Co rounded up to 32 rows, Ci rounded up to the column block bn (64 up to 64 channels, else 128).  Returns (wt, Cop, bn)."""
+    co, ci = w.shape[:2]
+    K, bn = 9 * co, 64 if ci <= 64 else 128
+    Kp, Cop = -(-K // 32) * 32, -(-ci // bn) * bn
+    wt = torch.zeros(Kp, Cop, dtype=torch.float32)
+    wt[:K, :ci] = w.flip(2, 3).permute(2, 3, 0, 1).reshape(K, ci)
+    return wt, Cop, bn
+
+
 class VggTrunk:
     """The packed convolution weights (device) and the launch sequence of the trunk."""
 
-    def __init__(self, convs, device):
+    def __init__(self, convs, device, transposed=False):
         from . import _lib
         self._lib = _lib
         self.convs = []
+        self.convs_t = []            # (Ci of the gradient GEMM, Co, Cop, bn, wt) per convolution, with `transposed`
         for stage in STAGES:
             for idx, ci, co in stage:
                 w, b = convs[idx]
@@ -66,6 +82,9 @@ class VggTrunk:
                 bp = torch.zeros(Cop, dtype=torch.float32)
                 bp[:co] = b
                 self.convs.append((cip, co, Cop, bn, wpk.to(device), bp.to(device)))
+                if transposed:
+                    wt, cop_t, bn_t = pack_transposed(w)
+                    self.convs_t.append((co, cip, cop_t, bn_t, wt.to(device)))
 
     def new_buffers(self, pixels, device):
         """The two ping-pong buffers for `pixels` level-0 pixels."""
@@ -84,10 +103,12 @@ class VggTrunk:
         lib.check(lib.lib.rick_inc_conv_f32(src, wpk.data_ptr(), bp.data_ptr(), ctypes.byref(a), lib.stream_ptr()),
                   'rick_inc_conv_f32')
 
-    def run(self, src, n, h, w, bufs, stage_dst, after_stage=None):
+    def run(self, src, n, h, w, bufs, stage_dst, after_stage=None, keep=None):
         """src: pointer to the NHWC4 input [n, h, w, 4].  Stage s's last convolution writes to the pointer stage_dst(s)
         ([n, h_s, w_s, C_s]; it must not alias bufs); after_stage(s, ptr, n, h_s, w_s), if given, is called once that
-        convolution is enqueued.  Returns (pointer, h, w) of the last stage's output."""
+        convolution is enqueued.  keep, if given, holds 13 pointers: convolution k that does not end a stage writes keep[k]
+        rather than a ping-pong buffer (the activations run_backward needs).  Returns (pointer, h, w) of the last stage's
+        output."""
         lib = self._lib
         stream = lib.stream_ptr()
         cur, k = src, 0
@@ -100,9 +121,48 @@ class VggTrunk:
             else:
                 flip = 0
             for j in range(len(stage)):
-                dst = stage_dst(s) if j == len(stage) - 1 else bufs[flip].data_ptr()
+                dst = stage_dst(s) if j == len(stage) - 1 else bufs[flip].data_ptr() if keep is None else keep[k]
                 self._conv(k, cur, n, h, w, dst)
                 cur, flip, k = dst, 1 - flip, k + 1
             if after_stage is not None:
                 after_stage(s, cur, n, h, w)
         return cur, h, w
+
+    def _conv_bwd(self, k, gout, n, h, w, mask, dst):
+        lib = self._lib
+        ci, co, cop, bn, wt = self.convs_t[k]
+        a = lib.IncConv()
+        a.N, a.IH, a.IW, a.Ci, a.KH, a.KW, a.SH, a.SW, a.PH, a.PW, a.OH, a.OW = n, h, w, ci, 3, 3, 1, 1, 1, 1, h, w
+        a.Co, a.Cop, a.bn, a.nseg = co, cop, bn, 1
+        for i in range(4):
+            a.seg_start[i], a.ldc[i], a.c0[i], a.dst[i] = (0, co, 0, dst) if i == 0 else (co, 0, 0, None)
+        lib.check(lib.lib.rick_inc_conv_bwd_f32(gout, wt.data_ptr(), mask, None, ctypes.byref(a), lib.stream_ptr()),
+                  'rick_inc_conv_bwd_f32')
+
+    def run_backward(self, n, h, w, acts, gbufs, tap_grad):
+        """The mirror of run: acts holds the pointers of the 13 stored activations of n images of h x w (a stage's last entry
+        is its output), gbufs three buffers of n * h * w * 64 floats.  tap_grad(s, ptr, n, h_s, w_s, relu) enqueues the
+        gradient that reaches stage s's output from outside into ptr [n, h_s, w_s, C_s]: through that output's ReLU for the
+        last stage (relu = True), as it stands for the others, whose ReLU the pool adjoint applies.  Returns the pointer (one
+        of gbufs) of the gradient with respect to the NHWC4 input [n, h, w, 4]."""
+        lib = self._lib
+        stream = lib.stream_ptr()
+        dims = [(h >> s, w >> s) for s in range(len(STAGES))]
+        k = sum(len(stage) for stage in STAGES) - 1
+        hs, ws = dims[-1]
+        cur, flip = gbufs[0].data_ptr(), 1
+        tap_grad(len(STAGES) - 1, cur, n, hs, ws, True)
+        for s in range(len(STAGES) - 1, -1, -1):
+            hs, ws = dims[s]
+            for j in range(len(STAGES[s]) - 1, -1, -1):
+                dst = gbufs[flip].data_ptr()
+                self._conv_bwd(k, cur, n, hs, ws, acts[k - 1] if j else None, dst)
+                cur, flip, k = dst, 1 - flip, k - 1
+            if s:
+                hs, ws = dims[s - 1]
+                tap_grad(s - 1, gbufs[2].data_ptr(), n, hs, ws, False)
+                dst = gbufs[flip].data_ptr()
+                lib.check(lib.lib.rick_lpips_maxpool2_bwd_f32(acts[k], gbufs[2].data_ptr(), cur, dst, n, hs, ws, CHANNELS[s - 1],
+                                                              stream), 'rick_lpips_maxpool2_bwd_f32')
+                cur, flip = dst, 1 - flip
+        return cur

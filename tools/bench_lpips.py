@@ -4,6 +4,10 @@ intra_lpips at the reference's defaults (1 000 samples at 256^2, 10 centres, 50 
 timed separately, plus its peak device memory.  Seeded synthetic weights (timing only).
 
   python tools/bench_lpips.py [--iters 10] [--skip-eval]
+  python tools/bench_lpips.py --backward [--iters 10] [--project-steps 1000]
+--backward measures the differentiable path instead (LPIPS.loss): at 256^2 and n = 1 and 25 the features forward alone and
+forward + loss + backward with respect to the image, and the wall time of a projection of one 256-px image
+(rick_amd/project.py) next to its generator part and its LPIPS part, each timed alone over the same number of steps.
 Prints a readable report and one JSON line."""
 import argparse
 import json
@@ -48,11 +52,77 @@ def timed(fn, iters):
     return e0.elapsed_time(e1) / 1e3 / iters
 
 
+def backward_report(args):
+    from rick_amd.lpips import LPIPS
+    from tests.lpips_f64 import synthetic_state_dict
+    dev, size = 'cuda', 256
+    sd = synthetic_state_dict(0)
+    flops = trunk_flops(size)
+    res = {'metric': 'lpips_vgg16_backward', 'gflop_per_image_forward': flops / 1e9}
+    for n in (1, 25):
+        net = LPIPS.load(sd, device=dev, batch=n)
+        x = torch.rand(n, 3, size, size, device=dev, generator=torch.Generator(dev).manual_seed(n)) * 2 - 1
+        tf = net.features(torch.rand(n, 3, size, size, device=dev, generator=torch.Generator(dev).manual_seed(100 + n)) * 2 - 1)
+        out = net.new_features(n)
+        xr = x.clone().requires_grad_(True)
+
+        def fwd_bwd():
+            return torch.autograd.grad(net.loss(xr, tf).sum(), xr)
+        t_f = timed(lambda: net.features(x, out=out), args.iters)
+        t_fb = timed(fwd_bwd, args.iters)
+        res.update({f'forward_ms_n{n}': t_f * 1e3, f'forward_backward_ms_n{n}': t_fb * 1e3, f'ratio_n{n}': t_fb / t_f,
+                    f'forward_tflops_n{n}': flops * n / t_f / 1e12})
+        print(f'N={n:3d}: features forward {t_f * 1e3:8.3f} ms ({flops * n / t_f / 1e12:5.1f} TFLOP/s)   forward + loss + backward '
+              f'{t_fb * 1e3:8.3f} ms   x{t_fb / t_f:.2f}', flush=True)
+        del net, tf, out
+        torch.cuda.empty_cache()
+    if args.project_steps > 0:
+        from rick_amd.models import Generator
+        from rick_amd.project import project
+        from rick_amd.synth import synth_state_dict
+        from tests.shapes import generator_shapes
+        steps = args.project_steps
+        g = Generator(size, 512, 8, channel_multiplier=2)
+        g.load_state_dict(synth_state_dict(generator_shapes(size)), strict=False)
+        g = g.to(dev).requires_grad_(False)
+        net = LPIPS.load(sd, device=dev, batch=1)
+        with torch.no_grad():
+            target = g([torch.randn(1, 512, device=dev, generator=torch.Generator(dev).manual_seed(5))], randomize_noise=False)[0]
+        project(g, target, net, steps=5, rng=torch.Generator().manual_seed(0))          # warm-up
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        _, _, losses = project(g, target, net, steps=steps, rng=torch.Generator().manual_seed(0))
+        torch.cuda.synchronize()
+        t_total = time.perf_counter() - t0
+        w = g.mean_latent(1000).detach().requires_grad_(True)
+        go = torch.randn(1, 3, size, size, device=dev)
+
+        def g_step():
+            img, _ = g([w + 0.0], input_is_latent=True, randomize_noise=False)
+            return torch.autograd.grad(img, w, go)
+        xr = target.clone().requires_grad_(True)
+        tf = net.features(target.flip(-1))
+        t_g = timed(g_step, min(steps, 50))
+        t_l = timed(lambda: torch.autograd.grad(net.loss(xr, tf).sum(), xr), min(steps, 50))
+        res.update({'project_steps': steps, 'project_total_s': t_total, 'project_generator_s': t_g * steps,
+                    'project_lpips_s': t_l * steps, 'project_loss_first': float(losses[0]), 'project_loss_last': float(losses[-1])})
+        print(f'projection of one {size}-px image, {steps} steps: {t_total:.2f} s; alone, the generator forward + backward is '
+              f'{t_g * steps:.2f} s and the LPIPS forward + backward {t_l * steps:.2f} s; loss {float(losses[0]):.4f} -> '
+              f'{float(losses[-1]):.4f}', flush=True)
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--iters', type=int, default=10)
     ap.add_argument('--skip-eval', action='store_true')
+    ap.add_argument('--backward', action='store_true')
+    ap.add_argument('--project-steps', type=int, default=1000)
     args = ap.parse_args()
+    if args.backward:
+        torch.backends.cudnn.allow_tf32 = False
+        torch.backends.cuda.matmul.allow_tf32 = False
+        return backward_report(args)
     from rick_amd.lpips import LPIPS, _cpu_taps, scale_input
     from tests.lpips_f64 import synthetic_state_dict
     torch.backends.cudnn.allow_tf32 = False
