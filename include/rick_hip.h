@@ -136,7 +136,13 @@ int rick_conv_pack_weight(const float *w, int64_t s_co, int64_t s_ci, int64_t s_
  * replaces one launch per layer and orientation).  `descs_device` is an array of n descriptors in DEVICE
  * memory; descriptor d owns blocks [blk_begin[d], blk_begin[d] + rick_conv_pack_blocks(Co, Ci)), in order;
  * total_blocks = the sum.  `w` need not be a whole tensor: any (s_co, s_ci, s_t) view, e.g. the transposed
- * view the data gradient uses. */
+ * view the data gradient uses.
+ * PAIRS: two descriptors that are the mutually transposed views of one storage (Co/Ci and s_co/s_ci swapped, same w, s_t,
+ * nslices) may name each other in `partner` (index + 1, 0 = none).  Where one of the two is a row view (s_t == 1,
+ * s_ci == nslices) and nslices <= 9, a launch that covers BOTH entries (both indices < n, < 1024) reads the source once and
+ * writes both images from one pass; the two then need no blocks of their own (an empty block range is allowed, and blocks they
+ * do own stay idle).  A launch with a smaller n — one captured before the partner was appended — packs the entry through its
+ * own blocks as before, so an entry that such a launch covers must keep them.  total_blocks may be 0. */
 typedef struct {
     const float *w;
     int64_t s_co, s_ci, s_t;
@@ -144,7 +150,7 @@ typedef struct {
     int Co, Ci, nslices;
     float scale;
     int blk_begin;
-    int reserved;
+    int partner;            /* index + 1 of the transposed view's descriptor, 0 = none */
 } rick_pack_desc;
 int rick_conv_pack_blocks(int Co, int Ci);
 int rick_conv_pack_weights_multi(const rick_pack_desc *descs_device, int n, int total_blocks, int split, void *stream);

@@ -130,12 +130,37 @@ extern "C" int rick_conv_pack_weight(const float *w, int64_t s_co, int64_t s_ci,
 // descriptor d with blk_begin[d] <= b < blk_begin[d+1]; a thread owns one (co, ci) of a 128 x 32 tile and
 // walks the tap slices (contiguous in memory for [O, I, kh, kw] parameters).
 #define PK_NS_MAX 16      // tap slices staged through LDS (RICK_MAX_TAPS); more: the per-thread tap walk
+
+// Paired descriptors (rick_pack_desc.partner = partner index + 1, mutually): a view and its transposed view of the same
+// storage — the forward operand and the data-gradient operand of one convolution.  pack_weight_pair_kernel reads the source
+// ONCE and writes both images; the per-view kernel below leaves the blocks of such a descriptor (if it owns any) idle.  A pair
+// is live only inside a launch that covers both entries (partner < n): a launch captured before the partner was appended
+// keeps packing its entry through the entry's own blocks.
+#define PK_PAIR_NS 9          // tap slices of a paired view (3 x 3); more stay on the per-view path
+#define PK_PAIR_MAXN 1024     // descriptors the pair kernel scans (region prefix in LDS)
+#define PK_PAIR_PITCH (32 * PK_PAIR_NS + 1)
+#define PK_PAIR_REGS (32 * 32 * PK_PAIR_NS / 256)
+__device__ __forceinline__ bool pack_row_view(const rick_pack_desc &a) { return a.s_t == 1 && a.s_ci == a.nslices; }
+// partner of descriptor d in a launch over n entries, -1: d is packed on its own
+__device__ __forceinline__ int pack_partner(const rick_pack_desc *__restrict__ descs, int d, int n) {
+    if (d >= PK_PAIR_MAXN) return -1;
+    const rick_pack_desc a = descs[d];
+    const int p = a.partner - 1;
+    if (p < 0 || p == d || p >= n || p >= PK_PAIR_MAXN || a.nslices > PK_PAIR_NS) return -1;
+    if (a.s_co < 0 || a.s_ci < 0 || a.s_co >= (1 << 26) || a.s_ci >= (1 << 26)) return -1;    // (32-bit offsets inside a region)
+    const rick_pack_desc b = descs[p];
+    if (b.partner - 1 != d || b.w != a.w || b.nslices != a.nslices || b.s_t != a.s_t || b.Co != a.Ci || b.Ci != a.Co ||
+        b.s_co != a.s_ci || b.s_ci != a.s_co)
+        return -1;
+    return pack_row_view(a) || pack_row_view(b) ? p : -1;
+}
 __global__ __launch_bounds__(256) void pack_weight_multi_kernel(const rick_pack_desc *__restrict__ descs, int n, int split) {
     __shared__ float sw[256 * PK_NS_MAX];
     int d = 0;
     for (int i = 1; i < n; i++)
         if ((int)blockIdx.x >= descs[i].blk_begin) d = i;
     const rick_pack_desc ds = descs[d];
+    if (ds.partner && pack_partner(descs, d, n) >= 0) return;      // both images come from pack_weight_pair_kernel
     cv_fp16_saturate();
     const int nchunks = (ds.Ci + CV_CK - 1) / CV_CK;
     const float pscale =
@@ -205,14 +230,148 @@ __global__ __launch_bounds__(256) void pack_weight_multi_kernel(const rick_pack_
     cv_sat_report(satm);
 }
 
+// One image's share of a staged region: 32 rows x 32 k x ns values -> whole 64-byte rows (hi and lo) of one 128 x 32 tile per
+// slice.  `sw` holds the region as [co][ci * ns + slice] at pitch P; TR reads it column-wise (rows of the image = ci).
+template <bool TR>
+__device__ __forceinline__ float pack_pair_emit(const float *__restrict__ sw, int P, int ns, const rick_pack_desc &im, int row0,
+                                                int k0, int split) {
+    float satm = 0.f;
+    if (k0 >= im.Ci) return satm;                        // (padding rows of the OTHER image: this one has no such chunk)
+    const int nchunks = (im.Ci + CV_CK - 1) / CV_CK;
+    const float pscale = reinterpret_cast<const float *>((const unsigned char *)im.packed + packed_tile_bytes(im.Co, im.Ci, ns))[1];
+    unsigned char *base = (unsigned char *)im.packed + ((int64_t)(row0 / CV_BM) * nchunks + k0 / CV_CK) * ns * CV_WSTEP_BYTES;
+    for (int it = threadIdx.x; it < 128 * ns; it += 256) {
+        const int gq = it & 3, r = (it >> 2) & 31, sl = it >> 7;
+        const bool row_ok = row0 + r < im.Co;
+        unsigned short h[8], l[8];
+#pragma unroll
+        for (int jj = 0; jj < 8; jj++) {
+            const int kk = gq * 8 + jj;
+            float v = (TR ? sw[kk * P + r * ns + sl] : sw[r * P + kk * ns + sl]) * im.scale * pscale;
+            if (!(row_ok && k0 + kk < im.Ci)) v = 0.f;
+            satm = fmaxf(satm, fabsf(v));
+            split1(v, h[jj], l[jj], split);
+        }
+        const int row = (row0 & (CV_BM - 1)) + r;
+        unsigned char *dst = base + (int64_t)sl * CV_WSTEP_BYTES + row * 64 + cv_swz(gq, row) * 16;
+        *reinterpret_cast<uint4 *>(dst) = make_uint4(h[0] | ((unsigned)h[1] << 16), h[2] | ((unsigned)h[3] << 16),
+                                                     h[4] | ((unsigned)h[5] << 16), h[6] | ((unsigned)h[7] << 16));
+        *reinterpret_cast<uint4 *>(dst + CV_WTILE_BYTES) = make_uint4(l[0] | ((unsigned)l[1] << 16), l[2] | ((unsigned)l[3] << 16),
+                                                                      l[4] | ((unsigned)l[5] << 16), l[6] | ((unsigned)l[7] << 16));
+    }
+    return satm;
+}
+
+// Both images of every live pair, the source read once.  Work unit: a region of 32 co x 32 ci x ns weights, read in memory order
+// (32 runs of 32 * ns floats of the pair's row view: s_t == 1, s_ci == ns), held in LDS, converted once per image (each with its
+// own scale and its own exponent from its own trailer) and written as whole 64-byte rows: 32 rows of tile (co0 / 128, ci0 / 32) of
+// the row view's image, 32 rows of tile (ci0 / 128, co0 / 32) of the transposed view's.  The region grid covers the 128-row padding
+// of both images, so every byte of both buffers is written as rick_conv_pack_weight writes it.  The grid is sized from the CU
+// count; a block walks regions blockIdx.x, + gridDim.x, ... and holds the NEXT region's values in registers (loads in flight)
+// while it converts and stores the current one from LDS.
+// LDS pitch 32 * ns + 1 floats (odd): the row-wise read walks rows at an odd bank stride, the column-wise read walks ci at stride
+// ns (odd for 1 x 1 and 3 x 3); what is left is a 2-way overlap between 16-byte granules, on a pass that moves 74 KB through LDS
+// per 110 KB of HBM traffic — a tenth of the block's HBM time.
+struct pack_pair_job {
+    rick_pack_desc R, T;      // row view, transposed view
+    int co0, ci0;
+};
+__device__ __forceinline__ pack_pair_job pack_pair_decode(const rick_pack_desc *__restrict__ descs, const int *s_incl, int nn, int g) {
+    int lo = 0, hi = nn - 1;
+    while (lo < hi) {                                      // first d with s_incl[d] > g
+        const int mid = (lo + hi) >> 1;
+        if (s_incl[mid] > g) hi = mid; else lo = mid + 1;
+    }
+    const int loc = g - (lo ? s_incl[lo - 1] : 0);
+    const rick_pack_desc a = descs[lo], b = descs[a.partner - 1];
+    pack_pair_job j;
+    const bool a_row = pack_row_view(a);
+    j.R = a_row ? a : b;
+    j.T = a_row ? b : a;
+    const int nci = cdiv(j.R.Ci, CV_BM) * 4;
+    j.co0 = loc / nci * 32;
+    j.ci0 = loc % nci * 32;
+    return j;
+}
+__device__ __forceinline__ void pack_pair_load(const pack_pair_job &j, float (&v)[PK_PAIR_REGS]) {
+    const int rowlen = 32 * j.R.nslices, cols = (j.R.Ci - j.ci0) * j.R.nslices;      // valid floats of a row from ci0 on (may be <= 0)
+    const int rows = j.R.Co - j.co0 < 32 ? j.R.Co - j.co0 : 32, s_co = (int)j.R.s_co;    // (pack_partner: s_co < 2^26)
+    const float *src = j.R.w + (int64_t)j.co0 * j.R.s_co + (int64_t)j.ci0 * j.R.nslices;   // uniform base, 32-bit lane offsets
+#pragma unroll
+    for (int i = 0; i < PK_PAIR_REGS; i++) {
+        const int e = threadIdx.x + i * 256, r = e / rowlen, c = e - r * rowlen;
+        v[i] = (r < rows && c < cols) ? src[r * s_co + c] : 0.f;
+    }
+}
+__global__ __launch_bounds__(256) void pack_weight_pair_kernel(const rick_pack_desc *__restrict__ descs, int n, int split) {
+    __shared__ float sw[32 * PK_PAIR_PITCH];
+    __shared__ int s_incl[PK_PAIR_MAXN];
+    __shared__ int s_wsum[4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int nn = n < PK_PAIR_MAXN ? n : PK_PAIR_MAXN;
+    int total = 0;                                         // regions of all live pairs; a pair's regions hang on its lower index
+    for (int base = 0; base < nn; base += 256) {
+        const int t = base + tid;
+        int x = 0;
+        if (t < nn && pack_partner(descs, t, n) > t) x = cdiv(descs[t].Co, CV_BM) * 4 * cdiv(descs[t].Ci, CV_BM) * 4;
+        for (int o = 1; o < 64; o <<= 1) {
+            const int y = __shfl_up(x, o, 64);
+            if (lane >= o) x += y;
+        }
+        if (lane == 63) s_wsum[wave] = x;
+        __syncthreads();
+        int add = total;
+        for (int w = 0; w < wave; w++) add += s_wsum[w];
+        if (t < nn) s_incl[t] = x + add;
+        total += s_wsum[0] + s_wsum[1] + s_wsum[2] + s_wsum[3];
+        __syncthreads();
+    }
+    if ((int)blockIdx.x >= total) return;
+    cv_fp16_saturate();
+    float satm = 0.f;
+    float v[PK_PAIR_REGS];
+    pack_pair_load(pack_pair_decode(descs, s_incl, nn, blockIdx.x), v);
+    for (int g = blockIdx.x; g < total; g += (int)gridDim.x) {
+        const pack_pair_job cur = pack_pair_decode(descs, s_incl, nn, g);
+        const int ns = cur.R.nslices, rowlen = 32 * ns, P = rowlen + 1;
+#pragma unroll
+        for (int i = 0; i < PK_PAIR_REGS; i++) {
+            const int e = tid + i * 256, r = e / rowlen;
+            if (r < 32) sw[r * P + (e - r * rowlen)] = v[i];
+        }
+        __syncthreads();
+        if (g + (int)gridDim.x < total)                    // in flight while this region is converted and stored
+            pack_pair_load(pack_pair_decode(descs, s_incl, nn, g + (int)gridDim.x), v);
+        satm = fmaxf(satm, pack_pair_emit<false>(sw, P, ns, cur.R, cur.co0, cur.ci0, split));
+        satm = fmaxf(satm, pack_pair_emit<true>(sw, P, ns, cur.T, cur.ci0, cur.co0, split));
+        __syncthreads();
+    }
+    cv_sat_report(satm);
+}
+
 extern "C" int rick_conv_pack_blocks(int Co, int Ci) { return cdiv(Co, CV_BM) * cdiv(Ci, CV_CK) * (CV_BM * CV_CK / 256); }
+
+static int pack_pair_grid() {
+    static int blocks = 0;                                 // 3 blocks of 41 KB LDS per CU
+    if (!blocks) {
+        int dev = 0, cus = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+            cus < 1)
+            cus = 256;
+        blocks = 3 * cus;
+    }
+    return blocks;
+}
 
 extern "C" int rick_conv_pack_weights_multi(const rick_pack_desc *descs_device, int n, int total_blocks, int split,
                                             void *stream) {
-    if (!descs_device || n < 1 || total_blocks < 1 || (split != 1 && split != 2)) return RICK_EINVAL;
+    if (!descs_device || n < 1 || total_blocks < 0 || (split != 1 && split != 2)) return RICK_EINVAL;
     hipLaunchKernelGGL(pack_exponent_multi_kernel, dim3((unsigned)n), dim3(256), 0, (hipStream_t)stream, descs_device);
-    hipLaunchKernelGGL(pack_weight_multi_kernel, dim3((unsigned)total_blocks), dim3(256), 0, (hipStream_t)stream,
-                       descs_device, n, split);
+    if (total_blocks)
+        hipLaunchKernelGGL(pack_weight_multi_kernel, dim3((unsigned)total_blocks), dim3(256), 0, (hipStream_t)stream,
+                           descs_device, n, split);
+    hipLaunchKernelGGL(pack_weight_pair_kernel, dim3((unsigned)pack_pair_grid()), dim3(256), 0, (hipStream_t)stream, descs_device,
+                       n, split);
     RICK_LAUNCH_STATUS();
 }
 

@@ -131,24 +131,39 @@ def _w_strides(w):
 
 # rick_pack_desc (include/rick_hip.h), 64 bytes
 _DESC = np.dtype([('w', '<u8'), ('s_co', '<i8'), ('s_ci', '<i8'), ('s_t', '<i8'), ('packed', '<u8'), ('Co', '<i4'),
-                  ('Ci', '<i4'), ('nslices', '<i4'), ('scale', '<f4'), ('blk_begin', '<i4'), ('reserved', '<i4')])
+                  ('Ci', '<i4'), ('nslices', '<i4'), ('scale', '<f4'), ('blk_begin', '<i4'), ('partner', '<i4')])
+_PAIR_NS, _PAIR_MAXN = 9, 1024      # conv.hip: PK_PAIR_NS, PK_PAIR_MAXN
+
+
+def _transposed_desc(d):
+    """The descriptor fields of the transposed view of `d` (without the destination)."""
+    w, s_o, s_i, s_t, _, O, I, ns, sc = d
+    return (w, s_i, s_o, s_t, I, O, ns, sc)
 
 
 class PackGroup:
     """All packed conv weights of one network, refreshed by ONE launch.
 
     The optimiser updates every parameter of a network together, so the first stale lookup after a step
-    repacks every (parameter view, orientation) the network has asked for so far — rick_conv_pack_weights_multi —
+    repacks every distinct parameter view the network has asked for so far — rick_conv_pack_weights_multi —
     instead of one pack launch + one allocation per layer and orientation.  Destination buffers and the device
     descriptor table persist across steps.
 
-    The pack launch may be captured into a hipGraph (RickTrainer._run), which bakes in the table pointer, the entry
-    count and the block count.  The table is therefore APPEND-ONLY at fixed capacity: a request registered after a
-    capture lands behind the entries the captured launch reads (its prefix, and the prefix's block ranges, never
-    change), and a table that has to be rebuilt (capacity exceeded, a parameter's storage moved) is retired, not
-    freed — replays keep reading valid memory."""
+    A request is identified by what determines its bytes — (storage pointer, shape, strides, scale) — not by the
+    caller's tag: the '/conv' and '/convT' operands of one view, and the '/T/T' view the double backward of a
+    transposed convolution asks for, are one buffer and one descriptor.  A view and its transposed view (forward and
+    data-gradient operand of one convolution) are PAIRED, whichever arrives first: the pack kernel then reads the
+    parameter once and writes both images, and neither needs blocks of the per-view kernel.
 
-    CAPACITY = 256          # descriptors per table (one per parameter view and orientation; a network needs < 100)
+    The pack launch may be captured into a hipGraph, which bakes in the table pointer, the entry count and the block
+    count.  The table is therefore APPEND-ONLY at fixed capacity: a request registered after a capture lands behind
+    the entries the captured launch reads; of those entries (`frozen`) only the partner field may still change — the
+    captured launch ignores a partner beyond its entry count and keeps packing the entry through the blocks it
+    owned at capture time, which it therefore keeps.  Entries no captured launch has seen are laid out afresh on
+    every registration.  A table that has to be rebuilt (capacity exceeded, a parameter's storage moved) is retired,
+    not freed — replays keep reading valid memory."""
+
+    CAPACITY = 256          # descriptors per table (one per distinct parameter view; a network needs < 100)
 
     def __init__(self):
         self.reqs = {}          # request key -> dict(param, buf, desc fields, stamp); insertion order == table order
@@ -156,39 +171,64 @@ class PackGroup:
         self.host = None        # host mirror
         self.n = 0              # entries in use
         self.total_blocks = 0
+        self.frozen = 0         # entries (and, in frozen_blocks, blocks) a captured launch covers
+        self.frozen_blocks = 0
         self.retired = []       # tables a captured graph may still reference
         self.epoch = 0          # bumped when this network's parameters were updated through raw pointers
         self.after_repack = []  # callables run behind the pack launch (weight-only side products: modconv.DemodBank's wsq)
+        self.tags = set()       # what callers asked for, by tag path (tools/bench_pack.py: requested against distinct views)
 
-    def _append(self, req):
-        """Write the request's descriptor behind the existing ones (host mirror + the one device entry)."""
-        dev = req['buf'].device
-        if self.table is None or self.n >= self.host.shape[0]:
-            cap = max(self.CAPACITY, 2 * self.n)
-            host = np.zeros(cap, dtype=_DESC)
+    @property
+    def paired(self):
+        return int(np.count_nonzero(self.host['partner'][:self.n])) if self.host is not None else 0
+
+    def _layout(self):
+        """Pair the entries and give block ranges to those the per-view kernel packs; entries below `frozen` keep
+        the ranges a captured launch knows.  Uploads the rows that changed."""
+        reqs = list(self.reqs.values())
+        n = len(reqs)
+        if self.table is None or n > self.host.shape[0]:
+            cap = max(self.CAPACITY, 2 * n)
             if self.table is not None:
-                host[:self.n] = self.host[:self.n]
                 self.retired.append(self.table)
-            self.host = host
-            self.table = torch.from_numpy(host.view(np.uint8).copy()).to(dev)
-        w, s_o, s_i, s_t, packed, O, I, ns, sc = req['desc']
-        self.host[self.n] = (w, s_o, s_i, s_t, packed, O, I, ns, sc, self.total_blocks, 0)
-        sz = _DESC.itemsize
-        self.table[self.n * sz:(self.n + 1) * sz].copy_(torch.from_numpy(self.host[self.n:self.n + 1].view(np.uint8).copy()))
-        self.total_blocks += lib.rick_conv_pack_blocks(O, I)
-        self.n += 1
+                self.frozen = self.frozen_blocks = 0          # nothing captured reads the new table
+            self.host = np.zeros(cap, dtype=_DESC)
+            self.table = torch.from_numpy(self.host.view(np.uint8).copy()).to(reqs[0]['buf'].device)
+        old = self.host[:n].copy()
+        index = {r['desc'][:4] + r['desc'][5:]: i for i, r in enumerate(reqs)}
+        blocks = self.frozen_blocks
+        for i, r in enumerate(reqs):
+            w, s_o, s_i, s_t, packed, O, I, ns, sc = r['desc']
+            j = index.get(_transposed_desc(r['desc']), i)
+            if index.get(_transposed_desc(reqs[j]['desc'])) != i:
+                j = i
+            row = (s_t == 1 and s_i == ns) or (s_t == 1 and s_o == ns)
+            paired = j != i and row and ns <= _PAIR_NS and max(i, j) < _PAIR_MAXN
+            if i < self.frozen:
+                begin = int(self.host['blk_begin'][i])
+            else:
+                begin = blocks
+                if not paired:
+                    blocks += lib.rick_conv_pack_blocks(O, I)
+            self.host[i] = (w, s_o, s_i, s_t, packed, O, I, ns, sc, begin, j + 1 if paired else 0)
+        self.n, self.total_blocks = n, blocks
+        diff = np.nonzero(old != self.host[:n])[0]
+        if diff.size:
+            lo, sz = int(diff[0]), _DESC.itemsize
+            self.table[lo * sz:n * sz].copy_(torch.from_numpy(self.host[lo:n].view(np.uint8).copy()))
 
     def _rebuild(self):
         """Some parameter's storage moved: a fresh table from the surviving requests (the old one is retired)."""
         if self.table is not None:
             self.retired.append(self.table)
-        self.table, self.host, self.n, self.total_blocks = None, None, 0, 0
-        for r in self.reqs.values():
-            self._append(r)
+        self.table, self.host, self.n, self.total_blocks, self.frozen, self.frozen_blocks = None, None, 0, 0, 0, 0
+        if self.reqs:
+            self._layout()
 
     def lookup(self, w, scale, key):
         param, tag = key
-        rk = (id(param), tag, float(scale), tuple(w.shape), w.stride(), w.data_ptr())
+        self.tags.add((id(param), tag, float(scale), tuple(w.shape), w.stride(), w.data_ptr()))
+        rk = (w.data_ptr(), tuple(w.shape), w.stride(), float(scale))
         req = self.reqs.get(rk)
         if req is None:
             w2, s_o, s_i, s_t = _w_strides(w)
@@ -202,11 +242,12 @@ class PackGroup:
             req = dict(param=param, off=w.data_ptr() - param.data_ptr(), buf=buf, stamp=None,
                        desc=(w.data_ptr(), s_o, s_i, s_t, buf.data_ptr(), O, I, kh * kw, float(scale)))
             self.reqs[rk] = req
-            self._append(req)
+            self._layout()
             # first use: pack just this one (the group launch takes over from the next refresh on)
             check(lib.rick_conv_pack_weight(w.data_ptr(), s_o, s_i, s_t, O, I, kh * kw, float(scale), _SPLIT,
                                             buf.data_ptr(), stream_ptr()), 'rick_conv_pack_weight')
             req['stamp'] = (param._version, _weights_epoch, self.epoch, _SPLIT)
+        param = req['param']
         if req['stamp'] != (param._version, _weights_epoch, self.epoch, _SPLIT):
             self._repack()
         return req['buf']
@@ -237,6 +278,8 @@ class PackGroup:
             cb()
         if not self.reqs:
             return
+        if torch.cuda.is_current_stream_capturing():      # a replay runs exactly these entries and blocks
+            self.frozen, self.frozen_blocks = self.n, self.total_blocks
         check(lib.rick_conv_pack_weights_multi(ptr(self.table), self.n, self.total_blocks, _SPLIT, stream_ptr()),
               'rick_conv_pack_weights_multi')
         for r in self.reqs.values():
