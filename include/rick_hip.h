@@ -690,6 +690,28 @@ int64_t rick_fc_workspace_floats(int M, int K, int N);
 int rick_fc_f32(const float *x, const float *wpk, const float *bias, float *ws, float *out, int M, int K, int N, int relu,
                 void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Gram — the Gram matrix of a few very long rows and its adjoint (rick_amd/cdc.py): the device side of the cross-domain
+ * distance-consistency loss, which needs the cosine similarity of whole generator feature maps between batch members.
+ * x is B rows (1 <= B <= 8) of n >= 1 fp32 values, row stride n, 64-bit indices.  A row is an unordered bag of values: any
+ * memory layout, as long as all rows of a call share it.
+ * rick_gram_f32: G [B][B] fp64 (device) = x x^T, one pass over x.  Block s takes the elements [s L, (s + 1) L) of every row,
+ *   L = 4096 ceil(n / (4096 * 1024)) (at most 1024 slices; the slicing depends on n only).  Thread l of the block owns the
+ *   elements s L + 4 l + 1024 k + {0, 1, 2, 3} (k ascending) and keeps one fp32 fma chain per pair (i, j >= i) over them in
+ *   that order; the 32, 16, ..., 1 xor butterfly adds the lanes, ((w0 + w1) + w2) + w3 the four waves, and the slice's
+ *   B (B + 1) / 2 sums go to ws (fp32, rick_gram_workspace_bytes(B, n) bytes).  A second launch adds the slices in ascending
+ *   order in fp64 and writes G[i][j] and G[j][i].  G is bit-identical from run to run and exactly symmetric, and G[i][j]
+ *   depends on rows i and j alone: the Gram matrix of two rows by themselves equals the entries of any batch that holds them,
+ *   bit for bit, wherever the rows lie.  Rows are read with 16-byte loads when x % 16 == 0 and n % 4 == 0, element by element
+ *   otherwise (the same sums).
+ * rick_rowmix_f32: y[k][t] = sum_m A[k][m] x[m][t], A [B][B] fp32 in device memory, y laid out like x (y != x).  Per element
+ *   one fp32 chain A[k][0] x[0][t], then fma(A[k][m], x[m][t], .) for m = 1 .. B - 1: with A = I it returns x (finite values;
+ *   -0 may come back as +0).  Reads B rows, writes B rows.
+ * No atomics, no host synchronisation, no allocation; every launch is on `stream` and can be captured. */
+int64_t rick_gram_workspace_bytes(int B, int64_t n);
+int rick_gram_f32(const float *x, int B, int64_t n, void *ws, double *G, void *stream);
+int rick_rowmix_f32(const float *A, const float *x, float *y, int B, int64_t n, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -191,6 +191,9 @@ SIGNATURES = {
     'rick_fc_packed_floats': (c_i64, [c_int, c_int]),
     'rick_fc_workspace_floats': (c_i64, [c_int, c_int, c_int]),
     'rick_fc_f32': (c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, c_fp]),
+    'rick_gram_workspace_bytes': (c_i64, [c_int, c_i64]),
+    'rick_gram_f32': (c_int, [c_fp, c_int, c_i64, c_fp, c_fp, c_fp]),
+    'rick_rowmix_f32': (c_int, [c_fp, c_fp, c_fp, c_int, c_i64, c_fp]),
 }
 
 if not os.path.exists(LIB_PATH):

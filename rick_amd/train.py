@@ -359,6 +359,8 @@ class TrainConfig:
     augment_p: float = 0.0                           # > 0: fixed p; 0: p adapted from the sign of D's real logits
     ada_target: float = 0.6
     ada_length: int = 500 * 1000
+    cdc_weight: float = 0.0                          # cross-domain distance consistency (rick_amd/cdc.py): the customary kl_wt, 1000
+    cdc_batch: int = 4                               # its batch (the reference still parses it: --feat_const_batch, :707)
 
 
 class AdaController:
@@ -402,11 +404,25 @@ def d_optim_filter(name):
 
 class RickTrainer:
     """One process / one GPU worth of the adaptation loop.  `dp` (rick_amd.dist.DataParallelGrads
-    or None) averages flat gradients over ranks with RCCL before each optimiser step."""
+    or None) averages flat gradients over ranks with RCCL before each optimiser step.  `g_source`: the frozen source
+    generator of the distance-consistency term (required when cfg.cdc_weight > 0; put in eval mode, gradients off)."""
 
-    def __init__(self, cfg, generator, discriminator, g_ema, d_ema, dp=None):
+    def __init__(self, cfg, generator, discriminator, g_ema, d_ema, dp=None, g_source=None):
         self.cfg, self.g, self.d, self.g_ema, self.d_ema, self.dp = cfg, generator, discriminator, g_ema, d_ema, dp
         self.device = next(generator.parameters()).device
+        self.g_source = g_source
+        if cfg.cdc_weight < 0 or (cfg.cdc_weight > 0 and cfg.cdc_batch < 2):
+            raise ValueError('RickTrainer: cdc_weight must be >= 0 and cdc_batch >= 2')
+        if cfg.cdc_weight > 0 and g_source is None:
+            raise ValueError('RickTrainer: cdc_weight > 0 needs the frozen source generator (g_source=)')
+        if g_source is not None:
+            if g_source is generator:
+                raise ValueError('RickTrainer: g_source must be a copy of the source generator, not the generator being trained')
+            if next(g_source.parameters()).device != self.device:
+                raise ValueError(f'RickTrainer: g_source on {next(g_source.parameters()).device}, generator on {self.device}')
+            g_source.eval()
+            for p in g_source.parameters():
+                p.requires_grad = False
         # packed conv weights: one refresh launch per network
         self._pack_groups = [op.register_pack_group(net) for net in (generator, discriminator)]
         self._ema_pack_groups = [op.register_pack_group(net) for net in (g_ema, d_ema)]
@@ -826,7 +842,29 @@ class RickTrainer:
         self._run('r1' if graph else None, fb, self.d_flat, self.d_optim)
         return self.losses['r1']
 
-    def g_step(self, noise, g_noise=None, graph=False):
+    def _cdc_term(self, cdc_noise=None, cdc_layers=None, g_noise=None):
+        """The unweighted distance-consistency loss (rick_amd/cdc.py) of one draw: z ~ N(0, I) [cdc_batch, latent] through the
+        frozen source generator (no grad) and the generator being trained, compared at one drawn feature layer per sample.
+        `g_noise`: fixed noise maps for both generators (drawn per call otherwise)."""
+        from . import cdc
+        cfg = self.cfg
+        z = cdc_noise if cdc_noise is not None else torch.randn(cfg.cdc_batch, cfg.latent, device=self.device)
+        layers = cdc_layers if cdc_layers is not None else cdc.draw_layers(self.g.n_latent, z.shape[0])
+        with torch.no_grad():
+            _, feats_s = self.g_source([z], noise=g_noise, return_feats=True)
+        _, feats_t = self.g([z], noise=g_noise, return_feats=True)
+        return cdc.distance_consistency_loss(feats_t, feats_s, layers)
+
+    def g_step(self, noise, g_noise=None, graph=False, cdc_noise=None, cdc_layers=None):
+        """Non-saturating G step.  With cfg.cdc_weight > 0 the distance-consistency term is added before the one backward():
+        its drawn layers change the launch list from step to step, so such a step is never captured — `graph=True` then runs
+        the eager path (its own mixing noise, no step graph) while every other step type keeps replaying.  `cdc_noise`
+        [cdc_batch, latent] and `cdc_layers` fix the term's draws (tests); `g_noise` also fixes its noise maps."""
+        cdc_on = self.cfg.cdc_weight > 0
+        if cdc_on and graph:
+            graph = False
+            if noise is None:
+                noise = mixing_noise(self.cfg.batch, self.cfg.latent, self.cfg.mixing, self.device)
         key = 'g' if graph else None
         batch = self.cfg.batch
         box = {}
@@ -847,9 +885,14 @@ class RickTrainer:
                     fake = augment_fused(fake, self._aug['g']['dev'])
                 fake_pred, _ = self.d(fake)
                 g_loss = g_nonsaturating_loss(fake_pred)
+                total = g_loss
+                if cdc_on:
+                    cdc_loss = self._cdc_term(cdc_noise, cdc_layers, g_noise)
+                    total = g_loss + self.cfg.cdc_weight * cdc_loss
+                    self.losses['cdc'] = cdc_loss.detach()
                 self._zero_grad(self.g_flat)
                 with op.deferred_sums(), op.wgrad_overlap():
-                    g_loss.backward()
+                    total.backward()
             self.losses['g'] = g_loss.detach()
         def pre():
             if graph:

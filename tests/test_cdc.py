@@ -1,0 +1,210 @@
+"""rick_amd.cdc on the CPU (the torch composition with fp64 accumulation) against the plain fp64 restatement tests/cdc_f64.py,
+and the trainer's wiring of the distance-consistency term.  CPU-only.
+
+The generator itself has no CPU path (its fused ops refuse CPU tensors, tests/test_op_cpu_dispatch.py), so the trainer tests here
+build the real 32-px networks and the real RickTrainer on the CPU and replace the two generators' ``forward`` by a small
+differentiable stand-in that returns a feature list; the whole ``g_step`` with the term runs in tests/test_gpu_cdc.py.
+
+Tolerances: the CPU composition forms fp64 Gram matrices of fp32 values; the restatement normalises each row first.  Both are
+fp64 throughout, n <= 4000 terms per sum: 1e-12 relative leaves three orders of magnitude over n * 2^-53 = 4.4e-13."""
+import copy
+
+import numpy as np
+import pytest
+import torch
+
+from rick_amd import cdc
+from tests.cdc_f64 import loss_f64, pairwise_cosine_f64, random_feats
+
+SHAPES = [(8, 4, 4), (8, 8, 8), (6, 8, 8), (4, 16, 16), (3, 5, 7)]
+CASES = {'distinct': [0, 1, 2, 3], 'repeated': [2, 4, 2, 2], 'one_layer': [3, 3, 3, 3]}
+TOL = 1e-12
+
+
+def _feats(seed=0, zero_row=False, B=4):
+    tgt, src = random_feats(SHAPES, B, seed)
+    if zero_row:
+        for f in tgt + src:
+            f[1].zero_()
+    return tgt, src
+
+
+def _rel(a, b):
+    return float((a.double() - b.double()).abs().max() / b.double().abs().max().clamp_min(1e-300))
+
+
+@pytest.mark.parametrize('case', list(CASES) + ['zero_row'])
+def test_loss_and_cosines_vs_restatement(case):
+    layers = CASES.get(case, [0, 1, 1, 3])
+    tgt, src = _feats(seed=len(case), zero_row=case == 'zero_row')
+    c = cdc.pairwise_cosine(tgt, layers)
+    ref = pairwise_cosine_f64(tgt, layers)
+    assert c.shape == (4, 3) and c.dtype == torch.float64
+    assert float((c - ref).abs().max()) <= TOL
+    if case == 'zero_row':          # the clamp: cosines with the all-zero sample are exactly 0, not NaN
+        assert torch.equal(c[1], torch.zeros(3, dtype=torch.float64)) and torch.equal(c[0, 0], torch.zeros((), dtype=torch.float64))
+    loss = cdc.distance_consistency_loss(tgt, src, layers)
+    ref = loss_f64(tgt, src, layers)
+    assert loss.dim() == 0 and loss.dtype == torch.float32
+    assert float(ref) > 1e-6                                   # the comparison is not between two zeros
+    assert abs(float(loss) - float(ref)) <= 2.0 ** -23 * abs(float(ref))          # the fp32 rounding of the returned value
+
+
+@pytest.mark.parametrize('case', list(CASES) + ['zero_row'])
+def test_gradient_vs_restatement(case):
+    layers = CASES.get(case, [0, 1, 1, 3])
+    tgt, src = _feats(seed=10 + len(case), zero_row=case == 'zero_row')
+    used = sorted(set(layers))
+    t32 = [f.clone().requires_grad_(True) for f in tgt]
+    g = torch.autograd.grad(cdc.distance_consistency_loss(t32, src, layers), [t32[l] for l in used])
+    t64 = [f.double().requires_grad_(True) for f in tgt]
+    gref = torch.autograd.grad(loss_f64(t64, src, layers), [t64[l] for l in used])
+    for a, b in zip(g, gref):
+        assert a.dtype == torch.float32 and torch.isfinite(a).all()
+        assert _rel(a, b) <= 2.0 ** -23 + TOL                  # fp64 everywhere, rounded to fp32 once at the end
+    unused = [l for l in range(len(SHAPES)) if l not in used]
+    if unused:
+        (gu,) = torch.autograd.grad(cdc.distance_consistency_loss(t32, src, layers), [t32[unused[0]]], allow_unused=True)
+        assert gu is None
+
+
+def test_batch_of_two_is_zero():
+    tgt, src = _feats(seed=3, B=2)
+    t = [f.clone().requires_grad_(True) for f in tgt]
+    loss = cdc.distance_consistency_loss(t, src, [1, 2])
+    assert float(loss.detach()) == 0.0                         # each row's softmax is over one entry
+    for gr in torch.autograd.grad(loss, [t[1], t[2]]):
+        assert not gr.any()
+
+
+def test_draw_layers_is_the_customary_draw():
+    for seed, n_latent, batch in ((0, 14, 4), (5, 8, 7), (9, 18, 2)):
+        ref = np.random.RandomState(seed).randint(1, n_latent - 1, batch)
+        assert np.array_equal(cdc.draw_layers(n_latent, batch, np.random.RandomState(seed)), ref)
+        np.random.seed(seed)
+        assert np.array_equal(cdc.draw_layers(n_latent, batch), ref)
+    assert set(np.unique(cdc.draw_layers(14, 4000, np.random.RandomState(1)))) == set(range(1, 13))
+
+
+def test_gram_is_layout_blind():
+    g = torch.Generator().manual_seed(4)
+    x = torch.randn(4, 24, 9, 7, generator=g) + 1.0
+    xc = x.clone().requires_grad_(True)
+    xl = x.clone().contiguous(memory_format=torch.channels_last).requires_grad_(True)
+    assert cdc._sample_dense(xl) and not xl.is_contiguous()
+    xs = x.clone()[:, :, ::2]                                   # not dense: copied
+    assert not cdc._sample_dense(xs)
+    Gc, Gl = cdc.gram(xc), cdc.gram(xl)
+    ref = x.flatten(1).double() @ x.flatten(1).double().t()
+    assert Gc.dtype == torch.float64 and torch.equal(Gc, Gc.t()) and torch.equal(Gl, Gl.t())
+    assert _rel(Gc, ref) <= TOL and _rel(Gl, ref) <= TOL
+    assert _rel(cdc.gram(xs), xs.flatten(1).double() @ xs.flatten(1).double().t()) <= TOL
+    w = torch.randn(4, 4, generator=g, dtype=torch.float64)
+    (gc,) = torch.autograd.grad((Gc * w).sum(), xc)
+    (gl,) = torch.autograd.grad((Gl * w).sum(), xl)
+    gref = ((w + w.t()) @ x.flatten(1).double()).view_as(x)
+    assert gl.stride() == xl.stride() and gc.is_contiguous()   # the gradient comes back in the layout of x
+    assert _rel(gc, gref) <= 2.0 ** -23 + TOL and _rel(gl, gref) <= 2.0 ** -23 + TOL
+
+
+def test_gram_refuses_other_inputs():
+    with pytest.raises(RuntimeError):
+        cdc.gram(torch.zeros(2, 3, dtype=torch.float64))
+    with pytest.raises(ValueError):
+        cdc.gram(torch.zeros(0, 3))
+    with pytest.raises(ValueError):
+        cdc.pairwise_cosine([torch.zeros(3, 5)], [0, 0])
+
+
+def test_create_graph_raises():
+    x = (torch.randn(3, 10, generator=torch.Generator().manual_seed(1))).requires_grad_(True)
+    with pytest.raises(RuntimeError, match='first order'):
+        torch.autograd.grad(cdc.gram(x).sum(), x, create_graph=True)
+
+
+# ---- trainer -------------------------------------------------------------------------------------------------------------------
+def _nets(size=32):
+    from rick_amd.models import Discriminator, Generator
+    torch.manual_seed(0)
+    g0 = Generator(size, 512, 2, channel_multiplier=1)
+
+    def build():
+        g, d = Generator(size, 512, 2, channel_multiplier=1), Discriminator(size, channel_multiplier=1)
+        g.load_state_dict(g0.state_dict())
+        return g, d
+    return build
+
+
+def _stand_in(gen):
+    """forward(styles, return_feats=True) -> (None, feats): 13 - (256 px) / 7 (32 px) small feature maps that depend on z and,
+    differentiably, on the generator's own convs.* weights."""
+    ws = [p for n, p in gen.named_parameters() if n.startswith('convs.') and n.endswith('conv.weight')]
+
+    def forward(styles, return_feats=False, noise=None, **kw):
+        z = styles[0]
+        feats = []
+        for k in range(gen.n_latent - 1):
+            w = ws[k % len(ws)].flatten()[:48].view(1, 3, 4, 4)
+            feats.append(torch.tanh(z[:, k:k + 48].reshape(-1, 3, 4, 4) + (k + 1.0) * w) + 1.0)
+        return None, feats
+    return forward
+
+
+def _trainer(weight, with_source=True):
+    from rick_amd.train import RickTrainer, TrainConfig
+    build = _nets()
+    g, d = build()
+    g_ema, d_ema = build()
+    src = build()[0] if with_source else None
+    cfg = TrainConfig(size=32, batch=2, n_mlp=2, warmup_iter=0, cdc_weight=weight, cdc_batch=4)
+    return RickTrainer(cfg, g, d, g_ema, d_ema, g_source=src), src
+
+
+def test_trainer_needs_a_frozen_source():
+    from rick_amd.train import TrainConfig
+    assert TrainConfig().cdc_weight == 0.0 and TrainConfig().cdc_batch == 4
+    with pytest.raises(ValueError, match='g_source'):
+        _trainer(1000.0, with_source=False)
+    tr, src = _trainer(1000.0)
+    assert not src.training and not any(p.requires_grad for p in src.parameters())
+    with pytest.raises(ValueError):
+        from rick_amd.train import RickTrainer
+        RickTrainer(tr.cfg, tr.g, tr.d, tr.g_ema, tr.d_ema, g_source=tr.g)
+
+
+def test_trainer_term_equals_the_stand_alone_loss():
+    tr, src = _trainer(1000.0)
+    with torch.no_grad():
+        for p in tr.g.parameters():                            # the adapted generator has moved away from the source
+            p.add_(0.05 * torch.randn(p.shape, generator=torch.Generator().manual_seed(p.numel())))
+    before = copy.deepcopy(src.state_dict())
+    tr.g.forward, src.forward = _stand_in(tr.g), _stand_in(src)
+    z = torch.randn(4, 512, generator=torch.Generator().manual_seed(2))
+    layers = [1, 3, 3, 5]
+    term = tr._cdc_term(z, layers)
+    with torch.no_grad():
+        ref = cdc.distance_consistency_loss(tr.g([z], return_feats=True)[1], src([z], return_feats=True)[1], layers)
+    assert float(ref) > 0 and torch.equal(term.detach(), ref)
+    term.backward()
+    got = [n for n, p in tr.g.named_parameters() if p.grad is not None and p.grad.any()]
+    assert got and all(n.startswith('convs.') for n in got)
+    assert all(p.grad is None for p in src.parameters())
+    after = src.state_dict()
+    assert all(torch.equal(before[k], after[k]) for k in before)
+    # the draws when none are given: cdc_batch latents on the trainer's device, layers from the customary draw
+    seen = {}
+    inner = tr.g.forward
+
+    def recording(styles, **kw):
+        seen['z'] = styles[0]
+        out = inner(styles, **kw)
+        seen['feats'] = out[1]
+        return out
+    tr.g.forward = recording
+    np.random.seed(0)
+    term = tr._cdc_term()
+    layers = np.random.RandomState(0).randint(1, tr.g.n_latent - 1, 4)
+    assert seen['z'].shape == (4, 512) and seen['z'].device == tr.device
+    with torch.no_grad():
+        ref = cdc.distance_consistency_loss(seen['feats'], src([seen['z']], return_feats=True)[1], layers)
+    assert torch.equal(term.detach(), ref)                     # the layers it drew are the customary draw's
