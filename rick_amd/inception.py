@@ -12,7 +12,8 @@ fid_score.py), as a ``feature_fn`` for ``rick_amd.evaluate``.
 Every BasicConv2d is conv -> BatchNorm(eps 1e-3) -> ReLU; the BN is folded into the convolution (in fp64, stored fp32) when
 the weights are loaded.  CUDA fp32 inputs run the HIP kernels of rick_amd/csrc/inception.hip (NHWC activations, one
 f32-input MFMA implicit GEMM per convolution, the 1x1 heads that share an input fused into one GEMM, concats written in
-place); CPU inputs run the same folded network as a plain fp32 torch composition.  The CUDA path is capture-safe at a
+place; operands, descriptors and launches by rick_amd/gemm_conv.py, the classifier's by rick_amd/fc.py); CPU inputs run the
+same folded network as a plain fp32 torch composition.  The CUDA path is capture-safe at a
 fixed N: the workspace is allocated once in ``load``, every launch goes to the caller's stream, branches run in order.
 
 ``InceptionV3Logits`` is the same trunk with torchvision's classifier head, the network behind the reference's Inception Score
@@ -26,11 +27,15 @@ bilinear resize to 299 x 299, then pool3 -> ``fc`` 2048 -> 1000.
 The launch plan takes its geometry from the input size (75 x 75 at least, torchvision's floor; H and W may differ) and sizes
 its buffers from a dry walk over the layer table.
 """
-import ctypes
 import re
 
 import torch
 import torch.nn.functional as F
+
+from . import fc as fc_ops
+from . import gemm_conv
+from .gemm_conv import out_hw as _out_hw
+from .netutil import check_images, cuda_device, get, load_dict
 
 EPS = 1e-3
 SIZE = 299
@@ -127,17 +132,8 @@ def fold(sd, last_block=3):
         raise KeyError(f'InceptionV3Features: unexpected key {extra[0]!r}')
     folded = {}
     for name, ci, co, (kh, kw), _, _ in units(last_block):
-        shapes = {'conv.weight': (co, ci, kh, kw), 'bn.weight': (co,), 'bn.bias': (co,), 'bn.running_mean': (co,),
-                  'bn.running_var': (co,)}
-        t = {}
-        for suffix, shape in shapes.items():
-            key = f'{name}.{suffix}'
-            if key not in sd:
-                raise KeyError(f'InceptionV3Features: missing key {key!r}')
-            v = torch.as_tensor(sd[key])
-            if tuple(v.shape) != shape:
-                raise ValueError(f'InceptionV3Features: key {key!r} has shape {tuple(v.shape)}, expected {shape}')
-            t[suffix] = v.detach().to('cpu', torch.float64)
+        t = {suffix: get(sd, f'{name}.{suffix}', (co, ci, kh, kw) if suffix == 'conv.weight' else (co,), 'InceptionV3Features',
+                         dtype=torch.float64) for suffix in TENSORS}
         scale = t['bn.weight'] / torch.sqrt(t['bn.running_var'] + EPS)
         w = t['conv.weight'] * scale[:, None, None, None]
         b = t['bn.bias'] - t['bn.running_mean'] * scale
@@ -203,10 +199,6 @@ def _cpu_forward(P, x, last_block, affine=True):
 
 
 # ---- CUDA: a launch plan over a workspace allocated once ----------------------------------------------------------------
-def _out_hw(h, w, k, s, p):
-    return (h + 2 * p[0] - k[0]) // s[0] + 1, (w + 2 * p[1] - k[1]) // s[1] + 1
-
-
 MIN_SIZE = 75                   # torchvision's floor: below it a stride-2 stage has no output left
 
 
@@ -320,49 +312,22 @@ class _Plan:
         return cur, h * w, c
 
     def _conv(self, us, P, src, h, w, ci, dsts):
-        """One GEMM for the units `us` (same input, same geometry); dsts[i] = (tensor, ldc, c0) of unit i."""
-        lib = self._lib
+        """One GEMM for the units `us` (same input, same geometry); dsts[i] = (tensor, ldc, c0) of unit i.  The descriptor is
+        built here, once; a run only sets its N."""
         k, s, p = us[0][3], us[0][4], us[0][5]
         assert all(u[3] == k and u[4] == s and u[5] == p for u in us)
         if self._bufs is None:
             return
-        ws = []
-        for u in us:
-            wt = P[u[0]][0]
-            if wt.shape[1] < ci:                      # the stem's 3 input channels, padded to 4
-                wt = F.pad(wt, (0, 0, 0, 0, 0, ci - wt.shape[1]))
-            ws.append(wt)
-        wt = torch.cat(ws, 0)                         # [Co, Ci, kh, kw]
-        bias = torch.cat([P[u[0]][1] for u in us])
-        Co = wt.shape[0]
-        K = k[0] * k[1] * ci
-        Kp = -(-K // 32) * 32
-        c64, c128 = -(-Co // 64) * 64, -(-Co // 128) * 128
-        bn = 128 if c128 == c64 else 64
-        Cop = c64 if bn == 64 else c128
-        wpk = torch.zeros(Kp, Cop, dtype=torch.float32)
-        wpk[:K, :Co] = wt.permute(2, 3, 1, 0).reshape(K, Co)
-        bp = torch.zeros(Cop, dtype=torch.float32)
-        bp[:Co] = bias
+        wpk, bp, cop, bn = gemm_conv.pack(torch.cat([P[u[0]][0] for u in us]), torch.cat([P[u[0]][1] for u in us]), ci_pad=ci)
         wpk, bp = wpk.to(self.dev), bp.to(self.dev)
         self.keep += [wpk, bp]
-        oh, ow = _out_hw(h, w, k, s, p)
-        a = lib.IncConv()
-        a.IH, a.IW, a.Ci, a.KH, a.KW, a.SH, a.SW, a.PH, a.PW, a.OH, a.OW = h, w, ci, k[0], k[1], s[0], s[1], p[0], p[1], oh, ow
-        a.Co, a.Cop, a.bn, a.nseg = Co, Cop, bn, len(us)
-        start = 0
-        for i in range(4):
-            if i < len(us):
-                t, ldc, c0 = dsts[i]
-                a.seg_start[i], a.ldc[i], a.c0[i], a.dst[i] = start, ldc, c0, t.data_ptr()
-                start += us[i][2]
-            else:
-                a.seg_start[i], a.ldc[i], a.c0[i], a.dst[i] = Co, 0, 0, None
-        in_ptr, w_ptr, b_ptr, ref = src.data_ptr(), wpk.data_ptr(), bp.data_ptr(), ctypes.byref(a)
+        a = gemm_conv.descriptor(self.batch, h, w, ci, k, s, p, cop, bn,
+                                 [(t.data_ptr(), ldc, c0, u[2]) for (t, ldc, c0), u in zip(dsts, us)])
+        in_ptr, w_ptr, b_ptr = src.data_ptr(), wpk.data_ptr(), bp.data_ptr()
 
         def run(n, stream):
             a.N = n
-            lib.check(lib.lib.rick_inc_conv_f32(in_ptr, w_ptr, b_ptr, ref, stream), 'rick_inc_conv_f32')
+            gemm_conv.forward(in_ptr, w_ptr, b_ptr, a, stream)
         self.steps.append(run)
 
     def _maxpool(self, src, h, w, c, dst, ldc, c0):
@@ -402,33 +367,24 @@ class InceptionV3Features:
             raise ValueError('InceptionV3Features: batch must be >= 1')
         self.dims, self.batch, self.block = dims, int(batch), BLOCK_BY_DIMS[dims]
         self.folded = folded
-        self.device = torch.device(device)
+        self.device = cuda_device(device)
         self._plan = None
         if self.device.type == 'cuda':
-            dev = self.device if self.device.index is not None else torch.device('cuda', torch.cuda.current_device())
-            self.device = dev
-            with torch.cuda.device(dev):
-                self._plan = _Plan(folded, self.block, self.batch, dev)
+            with torch.cuda.device(self.device):
+                self._plan = _Plan(folded, self.block, self.batch, self.device)
 
     @classmethod
     def load(cls, src, device='cuda', dims=2048, batch=100):
         """src: a path (torch.load, weights_only) or a state_dict, torchvision or reference-wrapper layout."""
-        if not isinstance(src, dict):
-            src = torch.load(src, map_location='cpu', weights_only=True)
         if dims not in BLOCK_BY_DIMS:
             raise ValueError(f'InceptionV3Features: dims must be one of {sorted(BLOCK_BY_DIMS)}, got {dims}')
-        return cls(fold(src, BLOCK_BY_DIMS[dims]), device=device, dims=dims, batch=batch)
+        return cls(fold(load_dict(src), BLOCK_BY_DIMS[dims]), device=device, dims=dims, batch=batch)
 
     def __call__(self, images):
-        if images.dim() != 4 or images.shape[1] != 3:
-            raise RuntimeError(f'InceptionV3Features: expected images [N, 3, H, W], got {tuple(images.shape)}')
-        if images.dtype != torch.float32:
-            raise RuntimeError(f'InceptionV3Features: images must be float32, got {images.dtype}')
+        check_images(images, 'InceptionV3Features', self.device, noun='extractor')
         if images.device.type == 'cpu':
             with torch.no_grad():
                 return _cpu_forward(self.folded, images, self.block)
-        if self._plan is None or images.device != self.device:
-            raise RuntimeError(f'InceptionV3Features: images on {images.device}, extractor loaded for {self.device}')
         x = images.detach().contiguous()
         N = x.shape[0]
         out = torch.empty((N, self.dims), device=x.device, dtype=torch.float32)
@@ -445,15 +401,7 @@ CLASSES, POOL3 = 1000, 2048
 
 def fc_from_state_dict(sd):
     """(fc.weight [1000, 2048], fc.bias [1000]) fp32 on the CPU; a missing or mis-shaped key is an error that names it."""
-    out = []
-    for key, shape in (('fc.weight', (CLASSES, POOL3)), ('fc.bias', (CLASSES,))):
-        if key not in sd:
-            raise KeyError(f'InceptionV3Logits: missing key {key!r}')
-        v = torch.as_tensor(sd[key])
-        if tuple(v.shape) != shape:
-            raise ValueError(f'InceptionV3Logits: key {key!r} has shape {tuple(v.shape)}, expected {shape}')
-        out.append(v.detach().to('cpu', torch.float32).contiguous())
-    return tuple(out)
+    return (get(sd, 'fc.weight', (CLASSES, POOL3), 'InceptionV3Logits'), get(sd, 'fc.bias', (CLASSES,), 'InceptionV3Logits'))
 
 
 def softmax_rows(logits):
@@ -504,23 +452,18 @@ class InceptionV3Logits:
         if self.size is not None and min(self.size) < MIN_SIZE:
             raise ValueError(f'InceptionV3Logits: size must be at least {MIN_SIZE} x {MIN_SIZE}, got {self.size}')
         self.classes = CLASSES
-        self.device = torch.device(device)
+        self.device = cuda_device(device)
         self._plan = None
         if self.device.type == 'cuda':
             from . import _lib
-            from .fc import FC_MAX_ROWS, pack_fc_weight
-            if self.device.index is None:
-                self.device = torch.device('cuda', torch.cuda.current_device())
             with torch.cuda.device(self.device):
                 self._plan = _Plan(folded, 3, self.batch, self.device, in_hw=self.size or (SIZE, SIZE),
                                    input_kernel='rick_inc_input_raw_f32')
-                wpk = pack_fc_weight(fc[0])
-                if wpk.numel() != _lib.lib.rick_fc_packed_floats(POOL3, CLASSES):
-                    raise RuntimeError(f'InceptionV3Logits: packed fc weight has {wpk.numel()} floats, the kernel expects '
-                                       f'{_lib.lib.rick_fc_packed_floats(POOL3, CLASSES)}')
+                wpk = fc_ops.pack_fc_weight(fc[0])
+                fc_ops.check_packed(wpk, POOL3, CLASSES, 'InceptionV3Logits')
                 self._wpk, self._bias = wpk.to(self.device), fc[1].to(self.device)
                 self._pool3 = torch.empty(self.batch * POOL3, device=self.device, dtype=torch.float32)
-                rows = min(self.batch, FC_MAX_ROWS)
+                rows = min(self.batch, fc_ops.FC_MAX_ROWS)
                 self._ws = torch.empty(_lib.lib.rick_fc_workspace_floats(rows, POOL3, CLASSES), device=self.device,
                                        dtype=torch.float32)
 
@@ -528,31 +471,22 @@ class InceptionV3Logits:
     def load(cls, src, device='cuda', batch=100, size=None):
         """src: a path (torch.load, weights_only) or a state_dict, torchvision or reference-wrapper layout, with fc.weight and
         fc.bias."""
-        if not isinstance(src, dict):
-            src = torch.load(src, map_location='cpu', weights_only=True)
+        src = load_dict(src)
         return cls(fold(src, 3), fc_from_state_dict(src), device=device, batch=batch, size=size)
 
-    def _run_fc(self, lo, m, out):
-        """Rows [lo, lo + m) of the pool3 workspace (m <= 64) through the classifier -> the same rows of out."""
-        from . import _lib as lib
-        lib.check(lib.lib.rick_fc_f32(self._pool3.data_ptr() + 4 * lo * POOL3, self._wpk.data_ptr(), self._bias.data_ptr(),
-                                      self._ws.data_ptr(), out.data_ptr() + 4 * lo * CLASSES, m, POOL3, CLASSES, 0,
-                                      lib.stream_ptr()), 'rick_fc_f32')
+    def _run_fc(self, n, out):
+        """Rows [0, n) of the pool3 workspace through the classifier -> the same rows of out."""
+        fc_ops.run_fc(self._pool3.data_ptr(), self._wpk.data_ptr(), self._bias.data_ptr(), self._ws.data_ptr(), out.data_ptr(), n,
+                      POOL3, CLASSES, 0)
 
     def _run(self, x, out):
         """x [n, 3, H, W] contiguous (n <= batch) -> out [n, 1000]: the trunk, pool3 into the workspace, fc in chunks of 64 rows."""
-        from .fc import FC_MAX_ROWS
-        n = x.shape[0]
         self._plan.run(x, self._pool3)
-        for lo in range(0, n, FC_MAX_ROWS):
-            self._run_fc(lo, min(FC_MAX_ROWS, n - lo), out)
+        self._run_fc(x.shape[0], out)
 
     @torch.no_grad()
     def __call__(self, images):
-        if images.dim() != 4 or images.shape[1] != 3:
-            raise RuntimeError(f'InceptionV3Logits: expected images [N, 3, H, W], got {tuple(images.shape)}')
-        if images.dtype != torch.float32:
-            raise RuntimeError(f'InceptionV3Logits: images must be float32, got {images.dtype}')
+        check_images(images, 'InceptionV3Logits', self.device)
         if self.size is not None and tuple(images.shape[2:]) != self.size:
             raise RuntimeError(f'InceptionV3Logits: loaded for images of {self.size}, got {tuple(images.shape[2:])}')
         if images.device.type == 'cpu':
@@ -563,8 +497,6 @@ class InceptionV3Logits:
                     x = F.interpolate(x, (SIZE, SIZE), mode='bilinear', align_corners=False)
                 out[lo:lo + self.batch] = F.linear(_cpu_forward(self.folded, x, 3, affine=False), *self.fc)
             return out
-        if self._plan is None or images.device != self.device:
-            raise RuntimeError(f'InceptionV3Logits: images on {images.device}, network loaded for {self.device}')
         x = images.detach().contiguous()
         N = x.shape[0]
         out = torch.empty((N, CLASSES), device=x.device, dtype=torch.float32)

@@ -38,9 +38,11 @@ convolutions' data gradients, the transposed filters packed at load), rick_lpips
 and the lin weights file (``lin{k}.model.1.weight``, the layout of lpips' ``weights/v0.1/vgg.pth``).
 """
 import ctypes
+import functools
 
 import torch
 
+from .netutil import check_images, cuda_device, get, load_dict
 from .vgg_trunk import CHANNELS, STAGES, VggTrunk, cpu_stages
 
 SHIFT = (-.030, -.088, -.188)
@@ -66,13 +68,7 @@ def _positions_per_slice(c):
 
 
 # ---- loading --------------------------------------------------------------------------------------------------------------
-def _get(sd, key, shape):
-    if key not in sd:
-        raise KeyError(f'LPIPS: missing key {key!r}')
-    v = torch.as_tensor(sd[key])
-    if tuple(v.shape) != tuple(shape):
-        raise ValueError(f'LPIPS: key {key!r} has shape {tuple(v.shape)}, expected {tuple(shape)}')
-    return v.detach().to('cpu', torch.float32).contiguous()
+_get = functools.partial(get, who='LPIPS')
 
 
 def _check_scaling(sd, key, ref):
@@ -133,12 +129,6 @@ def params_from_vgg(vgg, lin):
     lins = _lin_weights(lin, used_lin)
     _unknown(lin, used_lin, 'lin weights')
     return convs, lins
-
-
-def _load_dict(src):
-    if src is None or isinstance(src, dict):
-        return src
-    return torch.load(src, map_location='cpu', weights_only=True)
 
 
 # ---- features -------------------------------------------------------------------------------------------------------------
@@ -307,11 +297,9 @@ class LPIPS:
             raise ValueError('LPIPS: batch must be >= 1')
         self.convs, self.lins = convs, lins
         self.batch, self.size = int(batch), int(size)
-        self.device = torch.device(device)
+        self.device = cuda_device(device)
         self._plan, self.workspace_features, self._second, self._grad_ws = None, None, None, None
         if self.device.type == 'cuda':
-            if self.device.index is None:
-                self.device = torch.device('cuda', torch.cuda.current_device())
             with torch.cuda.device(self.device):
                 self._plan = _Plan(convs, lins, self.batch, self.size, self.device)
                 self.workspace_features = LpipsFeatures.empty(self.batch, self.size, self.size, self.device)
@@ -322,22 +310,15 @@ class LPIPS:
         if src is not None:
             if vgg is not None or lin is not None:
                 raise ValueError('LPIPS.load: pass either src, or vgg and lin, not both')
-            convs, lins = params_from_lpips(_load_dict(src))
+            convs, lins = params_from_lpips(load_dict(src))
         elif vgg is None or lin is None:
             raise ValueError('LPIPS.load: pass src, or both vgg and lin')
         else:
-            convs, lins = params_from_vgg(_load_dict(vgg), _load_dict(lin))
+            convs, lins = params_from_vgg(load_dict(vgg), load_dict(lin))
         return cls(convs, lins, device=device, batch=batch, size=size)
 
     def _check_images(self, x, what):
-        if x.dim() != 4 or x.shape[1] != 3:
-            raise RuntimeError(f'LPIPS: expected {what} [N, 3, H, W], got {tuple(x.shape)}')
-        if x.dtype not in (torch.float32, torch.uint8):
-            raise RuntimeError(f'LPIPS: {what} must be float32 or uint8, got {x.dtype}')
-        if min(x.shape[2:]) < 16:
-            raise ValueError(f'LPIPS: images must be at least 16 x 16, got {tuple(x.shape[2:])}')
-        if x.device.type != 'cpu' and x.device != self.device:
-            raise RuntimeError(f'LPIPS: {what} on {x.device}, network loaded for {self.device}')
+        check_images(x, 'LPIPS', self.device, what, dtypes=(torch.float32, torch.uint8), min_size=16)
 
     def new_features(self, n, h=None, w=None):
         return LpipsFeatures.empty(n, h or self.size, w or self.size, self.device)

@@ -27,10 +27,13 @@ torch composition.
 ``src`` is a path to (or the contents of) a torchvision ``vgg16`` state_dict: ``features.{0,2,5,...,28}.{weight,bias}``,
 ``classifier.{0,3}.{weight,bias}``; ``classifier.6.*`` is accepted and ignored.
 """
+import functools
+
 import torch
 import torch.nn.functional as F
 
-from .fc import FC_MAX_ROWS, pack_fc_weight  # noqa: F401  (pack_fc_weight is part of this module's surface)
+from .fc import FC_MAX_ROWS, check_packed, pack_fc_weight, run_fc
+from .netutil import check_images, cuda_device, get, load_dict
 from .vgg_trunk import STAGES, VggTrunk, cpu_stages
 
 SIZE = 224
@@ -39,13 +42,7 @@ FC_IN, FEATURES = 7 * 7 * 512, 4096
 
 
 # ---- loading --------------------------------------------------------------------------------------------------------------
-def _get(sd, key, shape):
-    if key not in sd:
-        raise RuntimeError(f'VGG16Fc2Features: missing key {key!r}')
-    v = torch.as_tensor(sd[key])
-    if tuple(v.shape) != tuple(shape):
-        raise RuntimeError(f'VGG16Fc2Features: key {key!r} has shape {tuple(v.shape)}, expected {tuple(shape)}')
-    return v.detach().to('cpu', torch.float32).contiguous()
+_get = functools.partial(get, who='VGG16Fc2Features', errors=(RuntimeError, RuntimeError))
 
 
 def params_from_vgg16(sd):
@@ -72,12 +69,6 @@ def permute_fc1(w):
     """fc1 weight [4096, 25088] with K in the reference's (c, y, x) flatten order -> K in the trunk's NHWC (y, x, c) order."""
     y, x, c = POOLED
     return w.view(w.shape[0], c, y, x).permute(0, 2, 3, 1).reshape(w.shape[0], FC_IN).contiguous()
-
-
-def _load_dict(src):
-    if isinstance(src, dict):
-        return src
-    return torch.load(src, map_location='cpu', weights_only=True)
 
 
 # ---- resize ---------------------------------------------------------------------------------------------------------------
@@ -120,21 +111,15 @@ class _Plan:
         for (w, b), relu in zip(fcs, (1, 0)):
             n, k = w.shape
             wpk = pack_fc_weight(permute_fc1(w) if k == FC_IN else w)
-            if wpk.numel() != lib.rick_fc_packed_floats(k, n):
-                raise RuntimeError(f'VGG16Fc2Features: packed fc weight has {wpk.numel()} floats, the kernel expects '
-                                   f'{lib.rick_fc_packed_floats(k, n)}')
+            check_packed(wpk, k, n, 'VGG16Fc2Features')
             self.fc.append((wpk.to(device), b.to(device), k, n, relu))
             ws = max(ws, lib.rick_fc_workspace_floats(rows, k, n))
         self.hidden = torch.empty(batch * FEATURES, **f32)
         self.ws = torch.empty(ws, **f32)
 
     def _fc(self, layer, src, rows, dst):
-        lib = self._lib
         wpk, b, k, n, relu = self.fc[layer]
-        for lo in range(0, rows, FC_MAX_ROWS):
-            m = min(FC_MAX_ROWS, rows - lo)
-            lib.check(lib.lib.rick_fc_f32(src + 4 * lo * k, wpk.data_ptr(), b.data_ptr(), self.ws.data_ptr(), dst + 4 * lo * n,
-                                          m, k, n, relu, lib.stream_ptr()), 'rick_fc_f32')
+        run_fc(src, wpk.data_ptr(), b.data_ptr(), self.ws.data_ptr(), dst, rows, k, n, relu)
 
     def run(self, x, out):
         """x [n, 3, H, W] fp32 contiguous, n <= batch -> out [n, 4096] (contiguous rows)."""
@@ -157,29 +142,22 @@ class VGG16Fc2Features:
             raise ValueError('VGG16Fc2Features: batch must be >= 1')
         self.convs, self.fcs = convs, fcs
         self.batch = int(batch)
-        self.device = torch.device(device)
+        self.device = cuda_device(device)
         self._plan = None
         if self.device.type == 'cuda':
-            if self.device.index is None:
-                self.device = torch.device('cuda', torch.cuda.current_device())
             with torch.cuda.device(self.device):
                 self._plan = _Plan(convs, fcs, self.batch, self.device)
 
     @classmethod
     def load(cls, src, device='cuda', batch=25):
         """src: a path or state_dict in torchvision's vgg16 layout."""
-        convs, fcs = params_from_vgg16(_load_dict(src))
+        convs, fcs = params_from_vgg16(load_dict(src))
         return cls(convs, fcs, device=device, batch=batch)
 
     @torch.no_grad()
     def __call__(self, x):
         """x [N, 3, H, W] fp32 in [-1, 1] -> fc2 features [N, 4096] fp32 on x's device."""
-        if x.dim() != 4 or x.shape[1] != 3:
-            raise RuntimeError(f'VGG16Fc2Features: expected images [N, 3, H, W], got {tuple(x.shape)}')
-        if x.dtype != torch.float32:
-            raise RuntimeError(f'VGG16Fc2Features: images must be float32, got {x.dtype}')
-        if x.device.type != 'cpu' and x.device != self.device:
-            raise RuntimeError(f'VGG16Fc2Features: images on {x.device}, network loaded for {self.device}')
+        check_images(x, 'VGG16Fc2Features', self.device)
         N = x.shape[0]
         if x.device.type == 'cpu':
             out = torch.empty((N, FEATURES), dtype=torch.float32)

@@ -7,11 +7,14 @@ but the first.  Activations are NHWC fp32; the input is NHWC4 (channel 3 = 0).
 
 With ``transposed=True`` the trunk also holds every filter packed transposed and rotated, and ``run_backward`` carries a
 gradient from the five stage outputs back to the NHWC4 input on rick_inc_conv_bwd_f32 and rick_lpips_maxpool2_bwd_f32 (data
-gradients only: the weights are constants)."""
-import ctypes
-
+gradients only: the weights are constants).  The GEMM operands, descriptors and launches are rick_amd/gemm_conv.py's."""
 import torch
 import torch.nn.functional as F
+
+from . import gemm_conv
+from .gemm_conv import pack_transposed  # noqa: F401  (part of this module's surface)
+
+K3 = ((3, 3), (1, 1), (1, 1))           # kernel, stride, padding of every convolution
 
 # (features index, Ci, Co) of the 13 convolutions, grouped by stage; a 2x2 max pool precedes every stage but the first
 STAGES = [[(0, 3, 64), (2, 64, 64)], [(5, 64, 128), (7, 128, 128)], [(10, 128, 256), (12, 256, 256), (14, 256, 256)],
@@ -50,17 +53,6 @@ def pingpong_need():
     return need
 
 
-def pack_transposed(w):
-    """w [Co, Ci, 3, 3] -> the data gradient's GEMM operand [Kp, Cop]: Wt[(ky, kx, co)][ci] = W[co][ci][2 - ky][2 - kx], K =
-    9 Co rounded up to 32 rows, Ci rounded up to the column block bn (64 up to 64 channels, else 128).  Returns (wt, Cop, bn)."""
-    co, ci = w.shape[:2]
-    K, bn = 9 * co, 64 if ci <= 64 else 128
-    Kp, Cop = -(-K // 32) * 32, -(-ci // bn) * bn
-    wt = torch.zeros(Kp, Cop, dtype=torch.float32)
-    wt[:K, :ci] = w.flip(2, 3).permute(2, 3, 0, 1).reshape(K, ci)
-    return wt, Cop, bn
-
-
 class VggTrunk:
     """The packed convolution weights (device) and the launch sequence of the trunk."""
 
@@ -72,18 +64,11 @@ class VggTrunk:
         for stage in STAGES:
             for idx, ci, co in stage:
                 w, b = convs[idx]
-                cip = -(-ci // 4) * 4
-                if cip != ci:                                       # the 3 input channels, padded to 4
-                    w = F.pad(w, (0, 0, 0, 0, 0, cip - ci))
-                K, bn = 9 * cip, 64 if co == 64 else 128
-                Kp, Cop = -(-K // 32) * 32, -(-co // bn) * bn
-                wpk = torch.zeros(Kp, Cop, dtype=torch.float32)
-                wpk[:K, :co] = w.permute(2, 3, 1, 0).reshape(K, co)
-                bp = torch.zeros(Cop, dtype=torch.float32)
-                bp[:co] = b
-                self.convs.append((cip, co, Cop, bn, wpk.to(device), bp.to(device)))
+                cip = -(-ci // 4) * 4                               # the 3 input channels, padded to 4
+                wpk, bp, cop, bn = gemm_conv.pack(w, b, ci_pad=cip)
+                self.convs.append((cip, co, cop, bn, wpk.to(device), bp.to(device)))
                 if transposed:
-                    wt, cop_t, bn_t = pack_transposed(w)
+                    wt, cop_t, bn_t = pack_transposed(w, ci_pad=cip)
                     self.convs_t.append((co, cip, cop_t, bn_t, wt.to(device)))
 
     def new_buffers(self, pixels, device):
@@ -93,15 +78,8 @@ class VggTrunk:
         return [torch.empty(int(pixels * need[0]), **f32), torch.empty(max(1, int(pixels * need[1])), **f32)]
 
     def _conv(self, k, src, n, h, w, dst):
-        lib = self._lib
         ci, co, cop, bn, wpk, bp = self.convs[k]
-        a = lib.IncConv()
-        a.N, a.IH, a.IW, a.Ci, a.KH, a.KW, a.SH, a.SW, a.PH, a.PW, a.OH, a.OW = n, h, w, ci, 3, 3, 1, 1, 1, 1, h, w
-        a.Co, a.Cop, a.bn, a.nseg = co, cop, bn, 1
-        for i in range(4):
-            a.seg_start[i], a.ldc[i], a.c0[i], a.dst[i] = (0, co, 0, dst) if i == 0 else (co, 0, 0, None)
-        lib.check(lib.lib.rick_inc_conv_f32(src, wpk.data_ptr(), bp.data_ptr(), ctypes.byref(a), lib.stream_ptr()),
-                  'rick_inc_conv_f32')
+        gemm_conv.forward(src, wpk.data_ptr(), bp.data_ptr(), gemm_conv.descriptor(n, h, w, ci, *K3, cop, bn, [(dst, co, 0, co)]))
 
     def run(self, src, n, h, w, bufs, stage_dst, after_stage=None, keep=None):
         """src: pointer to the NHWC4 input [n, h, w, 4].  Stage s's last convolution writes to the pointer stage_dst(s)
@@ -129,15 +107,8 @@ class VggTrunk:
         return cur, h, w
 
     def _conv_bwd(self, k, gout, n, h, w, mask, dst):
-        lib = self._lib
         ci, co, cop, bn, wt = self.convs_t[k]
-        a = lib.IncConv()
-        a.N, a.IH, a.IW, a.Ci, a.KH, a.KW, a.SH, a.SW, a.PH, a.PW, a.OH, a.OW = n, h, w, ci, 3, 3, 1, 1, 1, 1, h, w
-        a.Co, a.Cop, a.bn, a.nseg = co, cop, bn, 1
-        for i in range(4):
-            a.seg_start[i], a.ldc[i], a.c0[i], a.dst[i] = (0, co, 0, dst) if i == 0 else (co, 0, 0, None)
-        lib.check(lib.lib.rick_inc_conv_bwd_f32(gout, wt.data_ptr(), mask, None, ctypes.byref(a), lib.stream_ptr()),
-                  'rick_inc_conv_bwd_f32')
+        gemm_conv.backward(gout, wt.data_ptr(), mask, None, gemm_conv.descriptor(n, h, w, ci, *K3, cop, bn, [(dst, co, 0, co)]))
 
     def run_backward(self, n, h, w, acts, gbufs, tap_grad):
         """The mirror of run: acts holds the pointers of the 13 stored activations of n images of h x w (a stage's last entry

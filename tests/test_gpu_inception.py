@@ -1,7 +1,5 @@
 """GPU: the InceptionV3 feature extractor's HIP kernels (rick_amd/csrc/inception.hip) against fp64 torch, the whole network
 against the independent fp64 restatement (tests/inception_f64.py), and the extractor inside the FID loop."""
-import ctypes
-
 import pytest
 import torch
 import torch.nn.functional as F
@@ -24,34 +22,14 @@ def _nhwc(x):
 
 def _conv(x_nhwc, w, b, s, p, dsts, bn=None):
     """rick_inc_conv_f32 on w [Co, Ci, kh, kw] (Co = the concatenation of the segments), dsts = [(tensor, ldc, c0, ncols)]."""
-    L = _lib()
+    from rick_amd import gemm_conv
     N, IH, IW, Ci = x_nhwc.shape
-    Co, _, kh, kw = w.shape
-    K = kh * kw * Ci
-    Kp = -(-K // 32) * 32
-    bn = bn or 128
-    Cop = -(-Co // bn) * bn
-    wpk = torch.zeros(Kp, Cop)
-    wpk[:K, :Co] = w.permute(2, 3, 1, 0).reshape(K, Co)
-    bp = torch.zeros(Cop)
-    bp[:Co] = b
+    wpk, bp, Cop, bn = gemm_conv.pack(w, b, bn=bn)
     wpk, bp = wpk.to(DEV), bp.to(DEV)
-    a = L.IncConv()
-    OH, OW = (IH + 2 * p[0] - kh) // s[0] + 1, (IW + 2 * p[1] - kw) // s[1] + 1
-    a.N, a.IH, a.IW, a.Ci, a.KH, a.KW, a.SH, a.SW, a.PH, a.PW, a.OH, a.OW = N, IH, IW, Ci, kh, kw, s[0], s[1], p[0], p[1], OH, OW
-    a.Co, a.Cop, a.bn, a.nseg = Co, Cop, bn, len(dsts)
-    start = 0
-    for i in range(4):
-        if i < len(dsts):
-            t, ldc, c0, nc = dsts[i]
-            a.seg_start[i], a.ldc[i], a.c0[i], a.dst[i] = start, ldc, c0, t.data_ptr()
-            start += nc
-        else:
-            a.seg_start[i], a.ldc[i], a.c0[i], a.dst[i] = Co, 0, 0, None
-    L.check(L.lib.rick_inc_conv_f32(x_nhwc.data_ptr(), wpk.data_ptr(), bp.data_ptr(), ctypes.byref(a), L.stream_ptr()),
-            'rick_inc_conv_f32')
+    a = gemm_conv.descriptor(N, IH, IW, Ci, w.shape[2:], s, p, Cop, bn, [(t.data_ptr(), ldc, c0, nc) for t, ldc, c0, nc in dsts])
+    gemm_conv.forward(x_nhwc.data_ptr(), wpk.data_ptr(), bp.data_ptr(), a)
     torch.cuda.synchronize()
-    return OH, OW
+    return a.OH, a.OW
 
 
 def _rel(got, ref):

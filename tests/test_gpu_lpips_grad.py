@@ -2,8 +2,6 @@
 whole path (LPIPS.loss) against autograd through the fp64 restatement within 4 x the fp32 composition's own error
 (tests/test_lpips_grad.py: BASE), its exact properties (value bit-identical to net(x, y), run-to-run and batch invariance),
 graph capture, and the latent projector on a synthetic 64-px generator."""
-import ctypes
-
 import pytest
 import torch
 import torch.nn.functional as F
@@ -138,8 +136,8 @@ def _conv_case(ci, co, hw):
 def test_conv_data_gradient_vs_fp64(ci, co, hw, use_mask, use_add):
     """Every output is a sum of K = 9 ci exact fp32 products (and `add`) accumulated in fp32 in some fixed order: whatever the
     order, |error| <= (K + 1) U (sum |g| |W| + |add|) per element.  Masked elements are exactly 0."""
+    from rick_amd import gemm_conv
     from rick_amd.vgg_trunk import pack_transposed
-    L = _lib()
     gout, wf, act, add, ref, mag = _conv_case(ci, co, hw)
     n, (h, w) = gout.shape[0], hw
     cop_ = -(-co // 4) * 4                                               # the image's 3 channels travel as 4
@@ -150,14 +148,8 @@ def test_conv_data_gradient_vs_fp64(ci, co, hw, use_mask, use_add):
     gd, wd = gout.permute(0, 2, 3, 1).contiguous().to(DEV), wt.to(DEV)
     md, ad = (nhwc(act) if use_mask else None), (nhwc(add) if use_add else None)
     out = _guarded(n * h * w * cop_)
-    a = L.IncConv()
-    a.N, a.IH, a.IW, a.Ci, a.KH, a.KW, a.SH, a.SW, a.PH, a.PW, a.OH, a.OW = n, h, w, ci, 3, 3, 1, 1, 1, 1, h, w
-    a.Co, a.Cop, a.bn, a.nseg = cop_, cop, bn, 1
-    for i in range(4):
-        a.seg_start[i], a.ldc[i], a.c0[i], a.dst[i] = (0, cop_, 0, out.data_ptr()) if i == 0 else (cop_, 0, 0, None)
-    L.check(L.lib.rick_inc_conv_bwd_f32(gd.data_ptr(), wd.data_ptr(), None if md is None else md.data_ptr(),
-                                        None if ad is None else ad.data_ptr(), ctypes.byref(a), L.stream_ptr()),
-            'rick_inc_conv_bwd_f32')
+    a = gemm_conv.descriptor(n, h, w, ci, (3, 3), (1, 1), (1, 1), cop, bn, [(out.data_ptr(), cop_, 0, cop_)])
+    gemm_conv.backward(gd.data_ptr(), wd.data_ptr(), None if md is None else md.data_ptr(), None if ad is None else ad.data_ptr(), a)
     got = _take(out, (n, h, w, cop_)).permute(0, 3, 1, 2)
     if cop_ != co:
         pad = got[:, co:]

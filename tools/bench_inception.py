@@ -89,8 +89,7 @@ def score_mode(args):
             acc = torch.zeros(1, 2 * CLASSES + 1, device=dev, dtype=torch.float64)
 
             def head():
-                for lo in range(0, n, 64):
-                    net._run_fc(lo, min(64, n - lo), logits)
+                net._run_fc(n, logits)
                 p, s_, h = softmax_rows(logits)
                 accumulate_rows(acc, p, s_, h, 0, 1 << 40)
             t_net = timed(lambda: net(x), args.iters)
