@@ -712,6 +712,32 @@ int64_t rick_gram_workspace_bytes(int B, int64_t n);
 int rick_gram_f32(const float *x, int B, int64_t n, void *ws, double *G, void *stream);
 int rick_rowmix_f32(const float *A, const float *x, float *y, int B, int64_t n, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * EWC — the elastic-weight-consolidation penalty on the flat parameter buffers (rick_amd/ewc.py):
+ *   L = sum_i F_i (theta_i - theta*_i)^2,   d(weight L) / d theta_i = 2 weight F_i (theta_i - theta*_i),
+ * one pass over theta, anchor (theta*), fisher (F) and grad, n >= 0 fp32 values each at any 4-byte-aligned address; with every
+ * F_i = 1 it is the L2-SP penalty.
+ * rick_ewc_f32: for every i with (mask[i] & 3) == 0 (the bits of rick_masked_adam_f32; mask may be NULL: nothing is masked), in
+ *   fp32:  d = theta[i] - anchor[i];  t = fisher[i] * d;  grad[i] = fmaf(2.f * weight, t, grad[i])
+ *   — three roundings — and the fp64 term (double)fisher[i] * (double)d * (double)d (a rounded fp64 product, not contracted
+ *   into the sum).  A masked element adds no term and its grad[i] is not written.  Block b of rick_ewc_blocks(n) =
+ *   ceil(n / 4096) blocks of 256 threads owns the elements [4096 b, min(n, 4096 (b + 1))): the block -> element map depends on
+ *   n alone, never on the device or a grid size (4096 = four 16-byte loads per thread and stream: enough in flight to stream at
+ *   HBM rate, 5 800 blocks at the 256-px generator's size).  When the four streams share a 16-byte phase a block takes the 0 - 3
+ *   elements in front of its first 16-byte boundary one by one (element j to thread j), then groups of four with 16-byte loads
+ *   (group k to thread k % 256), then the 0 - 3 elements left (to threads 0 - 2); otherwise element j of the block goes to thread
+ *   j % 256.  A thread adds its terms in ascending index order; the 32, 16, ..., 1 xor butterfly adds the lanes,
+ *   ((w0 + w1) + w2) + w3 the four waves, and the block stores partials[b] (fp64, 8-byte aligned, rick_ewc_blocks(n) entries,
+ *   every one written).  The sum is bit-identical from run to run for given addresses modulo 16.  n == 0 launches nothing.
+ *   Moves 20 B per element, 21 B with a mask.
+ * rick_ewc_finish_f64: out[0] = sum of partials[0 .. nblocks), one block: thread t adds partials[t], partials[t + 256], ... in
+ *   ascending order, then the same butterfly and wave order — a function of nblocks alone.  nblocks == 0 writes 0.
+ * No atomics, no host synchronisation, no allocation; both launches are on `stream` and can be captured. */
+int64_t rick_ewc_blocks(int64_t n);
+int rick_ewc_f32(const float *theta, const float *anchor, const float *fisher, float *grad, const uint8_t *mask, int64_t n,
+                 float weight, double *partials, void *stream);
+int rick_ewc_finish_f64(const double *partials, int64_t nblocks, double *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -138,6 +138,7 @@ class MaskedFlatAdam:
         self.steps_dev = torch.zeros(len(flat.params), device=flat.flat.device, dtype=torch.int32)
         self.bc = torch.ones(8, 2, device=flat.flat.device, dtype=torch.float32)      # one row per run of equal step count
         self.mask = None            # uint8 flat: bit0 freeze, bit1 prune
+        self.before_step = None     # callable run at the top of step(): a term added to flat.grad after the gradient exchange
         self.last_runs = []         # [(first param, last param)] of the most recent step()
 
     def set_mask(self, mask):
@@ -156,6 +157,8 @@ class MaskedFlatAdam:
                 self.steps[i] += 1
 
     def step(self):
+        if self.before_step is not None:
+            self.before_step()
         fp = self.fp
         idx = fp.opt_idx
         active = {i: fp.params[i].requires_grad for i in idx}
@@ -361,6 +364,7 @@ class TrainConfig:
     ada_length: int = 500 * 1000
     cdc_weight: float = 0.0                          # cross-domain distance consistency (rick_amd/cdc.py): the customary kl_wt, 1000
     cdc_batch: int = 4                               # its batch (the reference still parses it: --feat_const_batch, :707)
+    ewc_weight: float = 0.0                          # elastic weight consolidation on the generator (rick_amd/ewc.py): the paper's 5e8
 
 
 class AdaController:
@@ -405,14 +409,20 @@ def d_optim_filter(name):
 class RickTrainer:
     """One process / one GPU worth of the adaptation loop.  `dp` (rick_amd.dist.DataParallelGrads
     or None) averages flat gradients over ranks with RCCL before each optimiser step.  `g_source`: the frozen source
-    generator of the distance-consistency term (required when cfg.cdc_weight > 0; put in eval mode, gradients off)."""
+    generator of the distance-consistency term (required when cfg.cdc_weight > 0; put in eval mode, gradients off).  `ewc`: the
+    anchor of the elastic-weight-consolidation term (required when cfg.ewc_weight > 0), given as what `set_ewc` takes: a pair
+    (source_state, fisher) of {name: tensor} mappings, fisher None for the L2-SP penalty."""
 
-    def __init__(self, cfg, generator, discriminator, g_ema, d_ema, dp=None, g_source=None):
+    def __init__(self, cfg, generator, discriminator, g_ema, d_ema, dp=None, g_source=None, ewc=None):
         self.cfg, self.g, self.d, self.g_ema, self.d_ema, self.dp = cfg, generator, discriminator, g_ema, d_ema, dp
         self.device = next(generator.parameters()).device
         self.g_source = g_source
         if cfg.cdc_weight < 0 or (cfg.cdc_weight > 0 and cfg.cdc_batch < 2):
             raise ValueError('RickTrainer: cdc_weight must be >= 0 and cdc_batch >= 2')
+        if cfg.ewc_weight < 0 or not math.isfinite(cfg.ewc_weight):
+            raise ValueError('RickTrainer: ewc_weight must be finite and >= 0')
+        if cfg.ewc_weight > 0 and ewc is None:
+            raise ValueError('RickTrainer: ewc_weight > 0 needs the anchor (ewc=(source_state, fisher))')
         if cfg.cdc_weight > 0 and g_source is None:
             raise ValueError('RickTrainer: cdc_weight > 0 needs the frozen source generator (g_source=)')
         if g_source is not None:
@@ -457,6 +467,35 @@ class RickTrainer:
         self._ada_sum = torch.zeros((), device=self.device) if cfg.augment and self.ada.adaptive else None
         if dp is not None:
             dp.attach(self.g_flat, self.d_flat)
+        self.ewc = None
+        if ewc is not None:
+            self.set_ewc(*ewc) if isinstance(ewc, (tuple, list)) else self.set_ewc(ewc)
+
+    # ---- elastic weight consolidation (rick_amd/ewc.py)
+    def set_ewc(self, source_state, fisher=None):
+        """Build the anchor of the EWC term on the generator's flat buffer (FlatParams has re-homed the parameters, so it can only
+        be built once the trainer exists): `source_state` {name: tensor} (the source generator's state_dict), `fisher` {name:
+        tensor} (ewc.estimate_fisher) or None for all ones.  An EwcAnchor built on this trainer's g_flat is taken as it is.
+        Captured steps are dropped: they read the previous anchor's buffers."""
+        from .ewc import EwcAnchor
+        if isinstance(source_state, EwcAnchor):
+            if source_state.flat is not self.g_flat:
+                raise ValueError("RickTrainer.set_ewc: the anchor must be built on this trainer's g_flat")
+            anchor = source_state
+        else:
+            anchor = EwcAnchor(self.g_flat, source_state, fisher)
+        if self.ewc is not None:
+            self.invalidate_graphs()
+        self.ewc = anchor
+        return anchor
+
+    def _ewc_term(self):
+        """MaskedFlatAdam.before_step of the G step: the averaged gradient is complete (every rank adds the identical term to the
+        identical gradient) and Adam is next; in the split data-parallel capture this lands in the optimiser graph."""
+        from .ewc import penalty_
+        a, mask = self.ewc, self.g_optim.mask
+        value = penalty_(a, self.cfg.ewc_weight, None if mask is None else mask[a.lo:a.hi])
+        self.losses['ewc'] = value.detach()     # a new alias of the anchor's result tensor: registered as an output of a capture
 
     # ---- gradient flags of the discriminator for the current stage (:202-211)
     def _set_d_stage(self, i):
@@ -725,7 +764,9 @@ class RickTrainer:
         rel = tuple(s - st[0] for s in st)
         # (+ whether the step gathers its latents from the pool: mapping-network parameters that become trainable after a
         # capture switch the step back to drawing and mapping its own noise)
-        return (active, rel, optim.lr, tuple(optim.betas), optim.eps, self._pool_ok())
+        # (+ the EWC term of the G step: whether its two launches are part of the capture, and the weight they carry)
+        return (active, rel, optim.lr, tuple(optim.betas), optim.eps, self._pool_ok(), self.cfg.ewc_weight > 0,
+                float(self.cfg.ewc_weight))
 
     def invalidate_graphs(self):
         """Drop every captured step (after loading a checkpoint or changing optimiser hyper-parameters)."""
@@ -899,7 +940,17 @@ class RickTrainer:
                 self._draw_inject(key)
             if aug:
                 self._aug_block('g', 1, batch)
-        self._run(key, fb, self.g_flat, self.g_optim, pre=pre if (graph or aug) else None, fb_head=head)
+        # the EWC term is added at the top of the optimiser step: after the gradient exchange (the eager data-parallel mode still
+        # has bucket all-reduces in flight when backward() returns), in the G step only (the path-length step has its own
+        # optimiser step: the term there would be weighted 1 + 1 / g_reg_every times)
+        if self.cfg.ewc_weight > 0:
+            if self.ewc is None:
+                raise ValueError('RickTrainer: ewc_weight > 0 needs the anchor (set_ewc)')
+            self.g_optim.before_step = self._ewc_term
+        try:
+            self._run(key, fb, self.g_flat, self.g_optim, pre=pre if (graph or aug) else None, fb_head=head)
+        finally:
+            self.g_optim.before_step = None
         return self.losses['g']
 
     def _mixed_latents(self, noise):
