@@ -738,6 +738,59 @@ int rick_ewc_f32(const float *theta, const float *anchor, const float *fisher, f
                  float weight, double *partials, void *stream);
 int rick_ewc_finish_f64(const double *partials, int64_t nblocks, double *out, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * KML — kernel modulation of the frozen filters (AdAM's rank-constrained KML; rick_amd/kml.py).  A layer's weight is viewed as
+ * W[co][ci][taps] (a row o is ci * taps contiguous floats); with factors a[co][R], b[ci][R] (R = rank, 1 ... 8), a snapshot W0
+ * and a per-row flag:
+ *   s[o,i] = sum_r a[o,r] b[i,r]      W^[o,i,t] = W0[o,i,t] (1 + s[o,i])       P[o,i] = sum_t G[o,i,t] W0[o,i,t]
+ *   da[o,r] = sum_i P[o,i] b[i,r]     db[i,r] = sum_{o flagged} P[o,i] a[o,r]           (flagged rows only; da = 0 elsewhere)
+ * W (the optimised slice of the flat parameter buffer), W0 and G (the flat gradient) are n floats in ONE layout; every a and b
+ * lies in one factor buffer `fac` of nfac floats, da / db at the same offsets in `dfac`.  All layers of a network go in one
+ * launch, driven by tables in DEVICE memory that the host builds when the flags change:
+ *   layers[nlayers]   rick_kml_layer, below
+ *   rows[nrows_total] per layer (from rows_off) its nrows flagged row indices, ascending
+ *   blocks[nblocks]   pairs (layer, group): block k works on rows [group rg, min(nrows, (group + 1) rg)) of the layer's list,
+ *                     rg = rick_kml_rows_per_group(ci, taps); sum of ngroups = nblocks
+ *   rowflags[nflags]  per layer (from flags_off) co bytes, non-zero = flagged
+ * A kernel checks every table entry it uses against n, nfac, nrows_total, npart and nflags and skips a layer that does not fit.
+ * Work and traffic are proportional to the flagged rows: nblocks == 0 launches nothing in apply and grad.
+ * rick_kml_apply_f32: writes W^ over the flagged rows of w, nothing else (no other row, no padding): s = a[o,0] b[i,0], then
+ *   fmaf(a[o,r], b[i,r], s) for r = 1 .. R - 1; m = 1 + s; W^ = W0 * m — fp32, no contraction.  a = 0 returns W0 bit for bit.
+ *   Reads W0, writes W^: 8 B per modulated element.
+ * rick_kml_grad_f32 + rick_kml_grad_finish_f32: one pass over G and W0 of the flagged rows (8 B per modulated element); P is
+ *   never stored.  P[o,i] = G[.,0] W0[.,0], then fmaf over t = 1 .. taps - 1.  A block owns whole rows.  The 256 threads of a
+ *   block are `slots` groups of `lanes` threads, lanes = the power of two >= min(U, 256), U = the units of a row (four
+ *   consecutive i when the vector form applies: grad, w0 and the layer's offset 16-byte aligned, ci % 4 == 0, taps 1 or 9 —
+ *   4 taps floats as `taps` 16-byte loads; one i otherwise, element by element); row k of a group goes to slot k % slots, unit
+ *   u of a row to lane u % lanes.  da[o,r]: a lane adds fmaf(P[o,i], b[i,r], .) over its i ascending, the lanes are added by
+ *   the xor butterfly (lanes / 2, ..., 1; with 128 / 256 lanes the 2 / 4 waves in ascending order after it): it depends on row
+ *   o and on b alone, whatever else is flagged.  db: the lane that owns i adds fmaf(P[o,i], a[o,r], .) over the rows of its
+ *   slot ascending, the slots are added ascending, and the block writes partials[part_off + group R ci + r ci + i].  The finish
+ *   launch adds a layer's partials in ascending group order into db[i,r] (0 for a layer without a flagged row) and writes 0
+ *   into da of every unflagged row.  No atomics; every element of dfac inside a layer has exactly one writer; results are
+ *   bit-identical from run to run (for given addresses modulo 16).  grad needs R * max(1024, max_ci) floats of LDS (<= 64 KB:
+ *   RICK_EINVAL otherwise); max_co / max_ci: the largest co / ci of the table.
+ * No host synchronisation, no allocation; every launch is on `stream`. */
+typedef struct {
+    int64_t off;              /* first element of the layer's weight in w / w0 / grad */
+    int64_t a_off, b_off;     /* first element of a[co][R] / b[ci][R] in fac (da / db in dfac) */
+    int64_t part_off;         /* first float of the layer's db partials: ngroups x R x ci */
+    int32_t co, ci, taps;
+    int32_t rows_off, nrows;  /* the layer's flagged rows in `rows` */
+    int32_t rg, ngroups;      /* rows per group, ceil(nrows / rg) */
+    int32_t flags_off;        /* first byte of the layer's row flags */
+} rick_kml_layer;
+int rick_kml_rows_per_group(int ci, int taps);
+int rick_kml_apply_f32(const float *w0, float *w, int64_t n, const float *fac, int64_t nfac, int rank,
+                       const rick_kml_layer *layers, int nlayers, const int32_t *rows, int64_t nrows_total,
+                       const int32_t *blocks, int nblocks, void *stream);
+int rick_kml_grad_f32(const float *grad, const float *w0, int64_t n, const float *fac, float *dfac, int64_t nfac,
+                      float *partials, int64_t npart, int rank, const rick_kml_layer *layers, int nlayers,
+                      const int32_t *rows, int64_t nrows_total, const int32_t *blocks, int nblocks, int max_ci, void *stream);
+int rick_kml_grad_finish_f32(const float *partials, int64_t npart, float *dfac, int64_t nfac, const uint8_t *rowflags,
+                             int64_t nflags, int rank, const rick_kml_layer *layers, int nlayers, int max_co, int max_ci,
+                             void *stream);
+
 #ifdef __cplusplus
 }
 #endif

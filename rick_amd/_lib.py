@@ -66,6 +66,12 @@ class LpipsLayers(ctypes.Structure):
     _fields_ = [('nlayers', c_int), ('nslices', c_int * 8), ('hw', c_int * 8)]
 
 
+class KmlLayer(ctypes.Structure):
+    """rick_kml_layer (include/rick_hip.h)."""
+    _fields_ = [('off', c_i64), ('a_off', c_i64), ('b_off', c_i64), ('part_off', c_i64), ('co', c_int), ('ci', c_int), ('taps', c_int),
+                ('rows_off', c_int), ('nrows', c_int), ('rg', c_int), ('ngroups', c_int), ('flags_off', c_int)]
+
+
 # name -> (restype, argtypes); every symbol declared in include/rick_hip.h
 SIGNATURES = {
     'rick_abi_version': (c_int, []),
@@ -197,6 +203,11 @@ SIGNATURES = {
     'rick_ewc_blocks': (c_i64, [c_i64]),
     'rick_ewc_f32': (c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, c_i64, c_f, c_fp, c_fp]),
     'rick_ewc_finish_f64': (c_int, [c_fp, c_i64, c_fp, c_fp]),
+    'rick_kml_rows_per_group': (c_int, [c_int, c_int]),
+    'rick_kml_apply_f32': (c_int, [c_fp, c_fp, c_i64, c_fp, c_i64, c_int, c_fp, c_int, c_fp, c_i64, c_fp, c_int, c_fp]),
+    'rick_kml_grad_f32': (c_int, [c_fp, c_fp, c_i64, c_fp, c_fp, c_i64, c_fp, c_i64, c_int, c_fp, c_int, c_fp, c_i64, c_fp, c_int,
+                                  c_int, c_fp]),
+    'rick_kml_grad_finish_f32': (c_int, [c_fp, c_i64, c_fp, c_i64, c_fp, c_i64, c_int, c_fp, c_int, c_int, c_int, c_fp]),
 }
 
 if not os.path.exists(LIB_PATH):

@@ -365,6 +365,7 @@ class TrainConfig:
     cdc_weight: float = 0.0                          # cross-domain distance consistency (rick_amd/cdc.py): the customary kl_wt, 1000
     cdc_batch: int = 4                               # its batch (the reference still parses it: --feat_const_batch, :707)
     ewc_weight: float = 0.0                          # elastic weight consolidation on the generator (rick_amd/ewc.py): the paper's 5e8
+    kml_rank: int = 0                                # kernel modulation of the frozen filters (rick_amd/kml.py): AdAM's rank, 1 ... 8
 
 
 class AdaController:
@@ -425,6 +426,8 @@ class RickTrainer:
             raise ValueError('RickTrainer: ewc_weight > 0 needs the anchor (ewc=(source_state, fisher))')
         if cfg.cdc_weight > 0 and g_source is None:
             raise ValueError('RickTrainer: cdc_weight > 0 needs the frozen source generator (g_source=)')
+        if isinstance(cfg.kml_rank, bool) or not isinstance(cfg.kml_rank, int) or not 0 <= cfg.kml_rank <= 8:
+            raise ValueError('RickTrainer: kml_rank must be an integer in 0 ... 8')
         if g_source is not None:
             if g_source is generator:
                 raise ValueError('RickTrainer: g_source must be a copy of the source generator, not the generator being trained')
@@ -467,6 +470,12 @@ class RickTrainer:
         self._ada_sum = torch.zeros((), device=self.device) if cfg.augment and self.ada.adaptive else None
         if dp is not None:
             dp.attach(self.g_flat, self.d_flat)
+        # kernel modulation of the frozen filters (cfg.kml_rank > 0): one adapter per network, stepped with the network's lr / betas
+        self.kml_g = self.kml_d = None
+        if cfg.kml_rank > 0:
+            from .kml import KmlState
+            self.kml_g = KmlState(self.g_flat, cfg.kml_rank, lr=self.g_optim.lr, betas=self.g_optim.betas)
+            self.kml_d = KmlState(self.d_flat, cfg.kml_rank, lr=self.d_optim.lr, betas=self.d_optim.betas)
         self.ewc = None
         if ewc is not None:
             self.set_ewc(*ewc) if isinstance(ewc, (tuple, list)) else self.set_ewc(ewc)
@@ -496,6 +505,26 @@ class RickTrainer:
         a, mask = self.ewc, self.g_optim.mask
         value = penalty_(a, self.cfg.ewc_weight, None if mask is None else mask[a.lo:a.hi])
         self.losses['ewc'] = value.detach()     # a new alias of the anchor's result tensor: registered as an output of a capture
+
+    # ---- kernel modulation (rick_amd/kml.py)
+    def _kml(self, flat):
+        return self.kml_g if flat is self.g_flat else self.kml_d
+
+    def kml_rows_from_masks(self):
+        """Flag "frozen and not pruned" on every modulated layer, from the index sets the masks were built from (idx_freeze_*,
+        zero_idx_*): pruned filters are never modulated.  Called when a Fisher sweep installs new masks; a no-op without KML."""
+        for kml, freeze, zero in ((self.kml_g, self.idx_freeze_g, self.zero_idx_g), (self.kml_d, self.idx_freeze_d, self.zero_idx_d)):
+            if kml is None:
+                continue
+            rows = {}
+            for name in kml.names:
+                f = np.zeros(kml.shape3[name][0], dtype=bool)
+                if freeze is not None and name in freeze:
+                    f[np.asarray(freeze[name], dtype=np.int64)] = True
+                if zero is not None and name in zero:
+                    f[np.asarray(zero[name], dtype=np.int64)] = False
+                rows[name] = torch.from_numpy(f)
+            kml.set_rows(rows)
 
     # ---- gradient flags of the discriminator for the current stage (:202-211)
     def _set_d_stage(self, i):
@@ -544,6 +573,8 @@ class RickTrainer:
     # (style-mixing index) is written into device scalars before the replay.  With data parallelism the capture is
     # split around the gradient all-reduce (forward/backward graph -> RCCL -> optimiser graph).
     def enable_graphs(self, on=True):
+        if on and self.cfg.kml_rank > 0:
+            raise RuntimeError('RickTrainer: hipGraph replay with kernel modulation (kml_rank > 0) is not supported')
         self.use_graphs = bool(on)
         if self.dp is not None:
             self.dp.hooks_enabled = not self.use_graphs      # a replayed backward runs no Python hooks
@@ -642,6 +673,9 @@ class RickTrainer:
         forward/backward graph and the step returns; the next step replays its head, THEN waits for the exchange, replays the
         pending optimiser graph and continues — the all-reduce of the D gradients travels while the generator forward
         runs (north star: "overlapped with the next micro-batch forward")."""
+        kml = self._kml(flat) if self.cfg.kml_rank > 0 else None
+        if kml is not None and key is not None:
+            raise RuntimeError('RickTrainer: a graph=True step with kernel modulation (kml_rank > 0) is not supported')
         if pre is not None:
             pre()
         st = None
@@ -661,7 +695,12 @@ class RickTrainer:
                 fb_head()
             fb()
             self._reduce(flat)
-            optim.step()
+            if kml is not None:                               # the averaged gradient: da / db are identical on every rank
+                kml.grads_()
+            optim.step()                                      # (the freeze bit leaves the modulated rows alone)
+            if kml is not None:
+                kml.adam_step()
+                kml.apply_()
             return
         split = self.dp is not None and getattr(self.dp, 'active', True)
         if 'graphs' not in st:
@@ -1078,6 +1117,7 @@ class RickTrainer:
             self.zero_idx_d = zero_idx_merge(self.zero_idx_d, prune_d)
         self.g_optim.set_mask(build_mask(self.g_flat, self.idx_freeze_g, self.zero_idx_g))
         self.d_optim.set_mask(build_mask(self.d_flat, self.idx_freeze_d, self.zero_idx_d))
+        self.kml_rows_from_masks()
         return acc_g, acc_d
 
     # ---- one iteration in the reference's order (:395-589, 697-698)
