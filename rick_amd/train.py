@@ -922,6 +922,14 @@ class RickTrainer:
         self._run('r1' if graph else None, fb, self.d_flat, self.d_optim)
         return self.losses['r1']
 
+    def _feature_pair(self, z, g_noise=None):
+        """The feature lists of one latent batch z through the generator being trained and through the frozen source generator
+        (no grad): (feats_t, feats_s).  `g_noise`: fixed noise maps for both generators (drawn per call otherwise)."""
+        with torch.no_grad():
+            _, feats_s = self.g_source([z], noise=g_noise, return_feats=True)
+        _, feats_t = self.g([z], noise=g_noise, return_feats=True)
+        return feats_t, feats_s
+
     def _cdc_term(self, cdc_noise=None, cdc_layers=None, g_noise=None):
         """The unweighted distance-consistency loss (rick_amd/cdc.py) of one draw: z ~ N(0, I) [cdc_batch, latent] through the
         frozen source generator (no grad) and the generator being trained, compared at one drawn feature layer per sample.
@@ -930,9 +938,7 @@ class RickTrainer:
         cfg = self.cfg
         z = cdc_noise if cdc_noise is not None else torch.randn(cfg.cdc_batch, cfg.latent, device=self.device)
         layers = cdc_layers if cdc_layers is not None else cdc.draw_layers(self.g.n_latent, z.shape[0])
-        with torch.no_grad():
-            _, feats_s = self.g_source([z], noise=g_noise, return_feats=True)
-        _, feats_t = self.g([z], noise=g_noise, return_feats=True)
+        feats_t, feats_s = self._feature_pair(z, g_noise)
         return cdc.distance_consistency_loss(feats_t, feats_s, layers)
 
     def g_step(self, noise, g_noise=None, graph=False, cdc_noise=None, cdc_layers=None):
