@@ -791,6 +791,43 @@ int rick_kml_grad_finish_f32(const float *partials, int64_t npart, float *dfac, 
                              int64_t nflags, int rank, const rick_kml_layer *layers, int nlayers, int max_co, int max_ci,
                              void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * DiffAugment — Differentiable Augmentation (Zhao et al. 2020), policy color,translation,cutout (rick_amd/diffaug.py), for given
+ * per-image draws.  Images are planar fp32 [N, 3, H, W], contiguous, H, W <= 16384, N <= 65535; the draws live in device memory
+ * (`params`, N entries), so a captured graph replays with new draws after one copy into the block.  Brightness b, saturation s and
+ * contrast c collapse to one affine map per image, and the whole operator is
+ *   y = Cut . Shift . (L x + b 1),    L x = (c s) x + c (1 - s) mean_ch(x) + (1 - c) mean_all(x)        (L is self-adjoint)
+ *   y[:, r, q] = (L x + b)[:, r + tr, q + tc] where that lies inside the image and (r, q) is outside the cut, else exactly 0;
+ * a stage that is left out carries its identity: b = 0, s = 1, c = 1, tr = tc = 0, an empty cut.
+ * rick_diffaug_fwd_f32: out = y (bias != 0) or its linear part (bias == 0: b taken as 0);
+ * rick_diffaug_adj_f32: gx = L . Shift^T . Cut . gy, the transpose of the linear part.
+ * Each is two launches on `stream`.  (1) Block k of ceil(3 H W / 4096) per image sums the elements [4096 k, 4096 (k + 1)) of the
+ *   image's 3 H W — the adjoint only those of gy that the shift keeps and the cut does not zero — in fp64: a thread adds its
+ *   elements in ascending order, the lanes by the 32, 16, ..., 1 xor butterfly, the waves as ((w0 + w1) + w2) + w3 (the order of
+ *   rick_ewc_f32), into ws[n * blocks + k].  (2) Every block re-adds its image's partials in ascending order, forms
+ *   mean = sum / (3 H W) and t = (1 - c) * mean + b in fp64 (no b in the adjoint and with bias == 0), rounds t once, and writes each
+ *   output element once as  fmaf(c * s, v, fmaf(c * (1 - s), m, t)),  m = ((v0 + v1) + v2) / 3 in fp32, v the three channels of the
+ *   source pixel (in the adjoint 0 where gy is not read); the forward writes exact zeros in the fill and the cut.
+ * With W % 4 == 0 and 16-byte aligned images the launches use 16-byte stores and, where the column shift is a multiple of four
+ * (launch 1: always), 16-byte loads.  No atomics; every output element and every partial has one writer; results are bit-identical
+ * from run to run (for given addresses modulo 16) and an image's result does not depend on N or on the other images.  `ws`:
+ * rick_diffaug_workspace_bytes() bytes, 8-byte aligned.  No host synchronisation, no allocation: capture-safe.
+ * RICK_EINVAL for a null pointer, N, H or W below 1 or above the limits, a misaligned pointer; nothing is launched then.  The draws
+ * are in device memory, which an entry point cannot read without a synchronisation: rick_diffaug_check_params checks a HOST copy of
+ * the block before its upload — RICK_EINVAL for |tr| >= H, |tc| >= W, a cut bound outside [0, H] / [0, W], a NaN — and the kernels
+ * force every field of a block they are given into the image, so no launch reads or writes outside its buffers. */
+typedef struct {
+    float b, s, c;
+    int tr, tc;
+    int r0, r1, c0, c1;       /* cut = rows [r0, r1) x cols [c0, c1), empty when r0 >= r1 or c0 >= c1 */
+    int pad;
+} rick_diffaug_param;         /* 40 B */
+int64_t rick_diffaug_workspace_bytes(int N, int H, int W);
+int rick_diffaug_check_params(const rick_diffaug_param *host_params, int N, int H, int W);
+int rick_diffaug_fwd_f32(const float *x, const rick_diffaug_param *params, void *ws, float *out, int N, int H, int W, int bias,
+                         void *stream);
+int rick_diffaug_adj_f32(const float *gy, const rick_diffaug_param *params, void *ws, float *gx, int N, int H, int W, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

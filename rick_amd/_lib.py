@@ -208,6 +208,10 @@ SIGNATURES = {
     'rick_kml_grad_f32': (c_int, [c_fp, c_fp, c_i64, c_fp, c_fp, c_i64, c_fp, c_i64, c_int, c_fp, c_int, c_fp, c_i64, c_fp, c_int,
                                   c_int, c_fp]),
     'rick_kml_grad_finish_f32': (c_int, [c_fp, c_i64, c_fp, c_i64, c_fp, c_i64, c_int, c_fp, c_int, c_int, c_int, c_fp]),
+    'rick_diffaug_workspace_bytes': (c_i64, [c_int, c_int, c_int]),
+    'rick_diffaug_check_params': (c_int, [c_fp, c_int, c_int, c_int]),
+    'rick_diffaug_fwd_f32': (c_int, [c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, c_fp]),
+    'rick_diffaug_adj_f32': (c_int, [c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_fp]),
 }
 
 if not os.path.exists(LIB_PATH):

@@ -20,6 +20,7 @@ from torch import autograd
 from . import op
 from ._lib import check, lib, ptr, stream_ptr
 from .augment import augment_fused
+from .diffaug import diffaug_fused
 
 
 # --------------------------------------------------------------------------- losses
@@ -366,6 +367,7 @@ class TrainConfig:
     cdc_batch: int = 4                               # its batch (the reference still parses it: --feat_const_batch, :707)
     ewc_weight: float = 0.0                          # elastic weight consolidation on the generator (rick_amd/ewc.py): the paper's 5e8
     kml_rank: int = 0                                # kernel modulation of the frozen filters (rick_amd/kml.py): AdAM's rank, 1 ... 8
+    diffaug: str = ''                                # DiffAugment policy (rick_amd/diffaug.py), e.g. 'color,translation,cutout'; '' = off
 
 
 class AdaController:
@@ -416,6 +418,13 @@ class RickTrainer:
 
     def __init__(self, cfg, generator, discriminator, g_ema, d_ema, dp=None, g_source=None, ewc=None):
         self.cfg, self.g, self.d, self.g_ema, self.d_ema, self.dp = cfg, generator, discriminator, g_ema, d_ema, dp
+        # DiffAugment (cfg.diffaug): the parsed policy; the alternative to ADA on the discriminator side, never both
+        self._diffaug_policy = None
+        if cfg.diffaug:
+            from .diffaug import parse_policy
+            self._diffaug_policy = parse_policy(cfg.diffaug)
+            if cfg.augment:
+                raise ValueError('RickTrainer: augment (ADA) and diffaug are alternatives; set one of them')
         self.device = next(generator.parameters()).device
         self.g_source = g_source
         if cfg.cdc_weight < 0 or (cfg.cdc_weight > 0 and cfg.cdc_batch < 2):
@@ -468,6 +477,10 @@ class RickTrainer:
         self.aug_source = None
         self._aug = {}
         self._ada_sum = torch.zeros((), device=self.device) if cfg.augment and self.ada.adaptive else None
+        # DiffAugment: the persistent device parameter blocks of the D / R1 / G steps, refilled by each step's `pre=` hook.
+        # `diffaug_source(n)`, when set, returns the parameter records of a call of n images instead of the sampler (tests).
+        self.diffaug_source = None
+        self._daug = {}
         if dp is not None:
             dp.attach(self.g_flat, self.d_flat)
         # kernel modulation of the frozen filters (cfg.kml_rank > 0): one adapter per network, stepped with the network's lr / betas
@@ -848,6 +861,23 @@ class RickTrainer:
         ent['calls'] = blocks
         return ent
 
+    def _diffaug_block(self, key, n_calls, batch, reverse=False):
+        """Host side of DiffAugment in a step (its `pre=` hook), the mechanism of _aug_block: one draw per call of the published
+        trainer, in its order, checked and uploaded into the step's persistent device parameter block."""
+        from . import diffaug as DA
+        ent = self._daug.get(key)
+        h, w = self.cfg.size, self.cfg.size
+        if ent is None:
+            ent = self._daug[key] = {'dev': torch.zeros(n_calls * batch * DA.PARAM_DTYPE.itemsize, dtype=torch.uint8,
+                                                        device=self.device), 'staging': DA.ParamStaging()}
+        blocks = []
+        for _ in range(n_calls):
+            rec = self.diffaug_source(batch) if self.diffaug_source is not None else DA.draw_params(batch, h, w, self._diffaug_policy)
+            blocks.append(DA.check_params(rec, h, w))
+        DA.upload_params(np.concatenate(blocks[::-1] if reverse else blocks), self.device, dst=ent['dev'], staging=ent['staging'])
+        ent['calls'] = blocks
+        return ent
+
     def _ada_after_d_step(self, batch):
         """Adaptive p (train_dynamic_update_prune.py:440-459) after a D step of `batch` images on this rank."""
         if self._ada_sum is None:
@@ -868,6 +898,7 @@ class RickTrainer:
         batch = real_img.shape[0]
 
         aug = self.cfg.augment
+        daug = self._diffaug_policy is not None
 
         def fb():
             with torch.no_grad():
@@ -879,6 +910,8 @@ class RickTrainer:
                 if aug:                          # augment(real), augment(fake) of the reference: one launch pair
                     x = augment_fused(x, self._aug['d']['dev'])
                     self._aug_real.copy_(x[batch:])           # the R1 step's input (a static buffer under graphs)
+                if daug:                         # DiffAugment(real), DiffAugment(fake): one launch pair over cat(fake, real)
+                    x = diffaug_fused(x, self._daug['d']['dev'])
             # one pass over cat(fake, real): identical to the reference's two calls (per-call minibatch-stddev
             # statistics are kept), half the launches and twice the GEMM rows per launch
             with self._sink():                   # conv weight gradients are added straight into the flat buffer
@@ -902,24 +935,32 @@ class RickTrainer:
                     self._aug_real = torch.empty_like(real_img)
                 # the reference draws real's (G, C) first, then fake's; the launch runs over cat(fake, real)
                 self._aug_block('d', 2, batch, reverse=True)
-        self._run(key, fb, self.d_flat, self.d_optim, pre=pre if (graph or aug) else None)
+            if daug:                             # the same order: real's draws first, the launch over cat(fake, real)
+                self._diffaug_block('d', 2, batch, reverse=True)
+        self._run(key, fb, self.d_flat, self.d_optim, pre=pre if (graph or aug or daug) else None)
         self._ada_after_d_step(batch)
         return self.losses['d']
 
     def r1_step(self, real_img, i=10 ** 9, graph=False):
         cfg = self.cfg
         self._set_d_stage(i)
+        daug = self._diffaug_policy is not None
+        batch = real_img.shape[0]
 
         def fb():
             real = real_img.detach().requires_grad_(True)
             with op.second_order():
-                real_pred, _ = self.d(real)
+                # DiffAugment (the convention of its authors' StyleGAN2 trainer): D sees a fresh draw of the augmented reals, the
+                # penalty is on the gradient w.r.t. the PLAIN reals — adjoint in the inner gradient, forward without offset in its
+                # backward
+                real_pred, _ = self.d(diffaug_fused(real, self._daug['r1']['dev']) if daug else real)
                 real_pred = real_pred.view(real.size(0), -1).mean(dim=1).unsqueeze(1)
                 r1_loss = d_r1_loss(real_pred, real)
                 self._zero_grad(self.d_flat)
                 (cfg.r1 / 2 * r1_loss * cfg.d_reg_every + 0 * real_pred[0]).backward()
             self.losses['r1'] = r1_loss.detach()
-        self._run('r1' if graph else None, fb, self.d_flat, self.d_optim)
+        self._run('r1' if graph else None, fb, self.d_flat, self.d_optim,
+                  pre=(lambda: self._diffaug_block('r1', 1, batch)) if daug else None)
         return self.losses['r1']
 
     def _feature_pair(self, z, g_noise=None):
@@ -963,12 +1004,15 @@ class RickTrainer:
                     box['fake'], _ = self.g(noise, noise=g_noise)
 
         aug = self.cfg.augment
+        daug = self._diffaug_policy is not None
 
         def fb():
             with self._sink(), self._d_frozen():
                 fake = box.pop('fake')
                 if aug:
                     fake = augment_fused(fake, self._aug['g']['dev'])
+                if daug:                         # with gradients: the adjoint carries them back to G
+                    fake = diffaug_fused(fake, self._daug['g']['dev'])
                 fake_pred, _ = self.d(fake)
                 g_loss = g_nonsaturating_loss(fake_pred)
                 total = g_loss
@@ -985,6 +1029,8 @@ class RickTrainer:
                 self._draw_inject(key)
             if aug:
                 self._aug_block('g', 1, batch)
+            if daug:
+                self._diffaug_block('g', 1, batch)
         # the EWC term is added at the top of the optimiser step: after the gradient exchange (the eager data-parallel mode still
         # has bucket all-reduces in flight when backward() returns), in the G step only (the path-length step has its own
         # optimiser step: the term there would be weighted 1 + 1 / g_reg_every times)
@@ -993,7 +1039,7 @@ class RickTrainer:
                 raise ValueError('RickTrainer: ewc_weight > 0 needs the anchor (set_ewc)')
             self.g_optim.before_step = self._ewc_term
         try:
-            self._run(key, fb, self.g_flat, self.g_optim, pre=pre if (graph or aug) else None, fb_head=head)
+            self._run(key, fb, self.g_flat, self.g_optim, pre=pre if (graph or aug or daug) else None, fb_head=head)
         finally:
             self.g_optim.before_step = None
         return self.losses['g']
