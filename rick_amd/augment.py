@@ -19,9 +19,9 @@ import math
 import numpy as np
 import torch
 import torch.nn.functional as F
-from torch.autograd import Function
 
 from .op import upfirdn2d
+from .param_block import ParamStaging, fused_launch, linear_pair, upload_params  # noqa: F401  (ParamStaging: exported here too)
 
 # sym6 decomposition low-pass filter (the reference's antialiasing kernel, non_leaking.py:9-22)
 SYM6 = (0.015404109327027373, 0.0034907120842174702, -0.11799011114819057, -0.048311742585633,
@@ -239,85 +239,14 @@ def aug_params(G, C, height, width, pads):
     return out
 
 
-class ParamStaging:
-    """Pinned, double-buffered host staging for parameter blocks: a buffer is refilled only after the copy that last read it
-    has completed (its event), so an in-flight host-to-device copy is never overwritten."""
-
-    def __init__(self):
-        self.bufs, self.events, self.k = [None, None], [None, None], 0
-
-    def upload(self, block, dst):
-        raw = block.view(np.uint8).reshape(-1)
-        k = self.k = 1 - self.k
-        if self.events[k] is not None:
-            self.events[k].synchronize()
-        if self.bufs[k] is None or self.bufs[k].numel() < raw.size:
-            self.bufs[k] = torch.empty(max(raw.size, 4096), dtype=torch.uint8, pin_memory=True)
-        buf = self.bufs[k][:raw.size]
-        buf.numpy()[:] = raw
-        dst.view(-1)[:raw.size].copy_(buf, non_blocking=True)
-        ev = self.events[k] = torch.cuda.Event()
-        ev.record()
-        return dst
+def _workspace(lib, n, h, w, device):
+    return torch.empty(int(lib.rick_augment_workspace_floats(n, h, w)), device=device, dtype=torch.float32)
 
 
-_staging = ParamStaging()
-
-
-def upload_params(block, device, dst=None, staging=None):
-    """Copy a parameter block to the device: into `dst` (a persistent uint8 tensor that captured graphs read) or a new tensor."""
-    if dst is None:
-        dst = torch.empty(block.nbytes, dtype=torch.uint8, device=device)
-    elif dst.numel() < block.nbytes:
-        raise RuntimeError(f'augment: parameter block of {block.nbytes} bytes does not fit {dst.numel()}')
-    return (staging or _staging).upload(block, dst)
-
-
-def _launch(entry, x, params, **kw):
-    from ._lib import check, lib, ptr, require_cuda_f32, stream_ptr
-    require_cuda_f32(x)
-    x = x.contiguous()
-    n, c, h, w = x.shape
-    if c != 3 or params.numel() < n * PARAM_DTYPE.itemsize or not params.is_cuda:
-        raise RuntimeError(f'augment: needs [N, 3, H, W] images and N parameter entries; got {tuple(x.shape)}, {params.numel()} bytes')
-    ws = torch.empty(int(lib.rick_augment_workspace_floats(n, h, w)), device=x.device, dtype=torch.float32)
-    y = torch.empty_like(x)
-    if entry == 'fwd':
-        check(lib.rick_augment_fwd_f32(ptr(x), ptr(params), ptr(ws), ptr(y), n, h, w, int(kw['bias']), stream_ptr()),
-              'rick_augment_fwd_f32')
-    else:
-        check(lib.rick_augment_adj_f32(ptr(x), ptr(params), ptr(ws), ptr(y), n, h, w, stream_ptr()), 'rick_augment_adj_f32')
-    return y
-
-
-class AugmentFn(Function):
-    """y = augment(x) for fixed per-sample transforms (`bias`: with the colour offset).  Linear in x up to the offset: its
-    backward is AugmentAdjFn, whose backward is this map without the offset — closed under differentiation to any order.
-    No gradient flows to the parameters (the reference's matrices come from the sampler)."""
-
-    @staticmethod
-    def forward(ctx, x, params, bias=True):
-        ctx.save_for_backward(params)
-        return _launch('fwd', x, params, bias=bias)
-
-    @staticmethod
-    def backward(ctx, gy):
-        (params,) = ctx.saved_tensors
-        return AugmentAdjFn.apply(gy, params), None, None
-
-
-class AugmentAdjFn(Function):
-    """gx = (linear part of augment)^T gy."""
-
-    @staticmethod
-    def forward(ctx, gy, params):
-        ctx.save_for_backward(params)
-        return _launch('adj', gy, params)
-
-    @staticmethod
-    def backward(ctx, gg):
-        (params,) = ctx.saved_tensors
-        return AugmentFn.apply(gg, params, False), None
+# y = augment(x) for fixed per-sample transforms (`bias`: with the colour offset) and the adjoint of its linear part, each the other's
+# backward; no gradient flows to the parameters (the reference's matrices come from the sampler).
+AugmentFn, AugmentAdjFn = linear_pair(fused_launch('augment', PARAM_DTYPE.itemsize, 'rick_augment', _workspace),
+                                      'AugmentFn', 'AugmentAdjFn')
 
 
 def augment_fused(img, params):

@@ -49,6 +49,23 @@ __device__ __forceinline__ float block_sum_256(float v, float *red /* >= 4 float
     return red[0] + red[1] + red[2] + red[3];
 }
 
+// The fp64 pair, with a FIXED order that its callers state as a contract (run-to-run identical, batch-invariant sums): the
+// 32, 16, ..., 1 xor butterfly over the lanes, then ((w0 + w1) + w2) + w3 over the four waves of a 256-thread block.
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+// Valid in thread 0.  ONE barrier, between the waves' writes and the reads — unlike block_sum_256 there is no leading barrier, so
+// `red` must not be in use by another wave on entry: a caller that reuses `red` puts its own barrier between the calls.
+__device__ __forceinline__ double block_sum_256_f64(double v, double *red /* 4 doubles of LDS */) {
+    v = wave_sum_f64(v);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return ((red[0] + red[1]) + red[2]) + red[3];
+}
+
 // 16-byte load through a pointer that is KNOWN to address global memory.  Pointers read from descriptor tables are generic
 // to the compiler (FLAT loads: 64-bit per-lane address pairs, LDS / scratch aperture checks); this form yields
 // `global_load_dwordx4 v, v_off, s[base]`.

@@ -11,20 +11,6 @@
 #define DA_PIX 1024            // pixels per 256-thread block of the elementwise launch: four per thread, three channels each
 #define DA_MAXDIM (1 << 14)    // H, W <= 16384: 3 H W fits an int
 
-// The butterfly and wave order of ewc.hip: 32, 16, ..., 1 xor over the lanes, then ((w0 + w1) + w2) + w3; valid in thread 0.
-__device__ __forceinline__ double da_wave_sum_f64(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
-__device__ __forceinline__ double da_block_sum_256_f64(double v, double *red /* 4 doubles of LDS */) {
-    v = da_wave_sum_f64(v);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((red[0] + red[1]) + red[2]) + red[3];
-}
-
 // An image's geometry with every field forced into the image: whatever the parameter block holds, no index leaves [0, H) x [0, W)
 // (rick_diffaug_check_params rejects such a block on the host; the kernels stay memory-safe without it).
 struct da_geom {
@@ -94,7 +80,7 @@ __global__ __launch_bounds__(256) void da_sum_kernel(const float *__restrict__ x
             acc += (double)xi[j];
         }
     }
-    acc = da_block_sum_256_f64(acc, red);
+    acc = block_sum_256_f64(acc, red);
     if (threadIdx.x == 0) partials[(int64_t)n * gridDim.x + blockIdx.x] = acc;
 }
 

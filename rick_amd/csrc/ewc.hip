@@ -7,20 +7,6 @@
 
 #define EWC_CHUNK 4096         // elements per 256-thread block (rick_ewc_blocks): four float4 per thread and stream
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
-// The 32, 16, ..., 1 xor butterfly over the lanes, then ((w0 + w1) + w2) + w3 over the four waves; valid in thread 0.
-__device__ __forceinline__ double block_sum_256_f64(double v, double *red /* 4 doubles of LDS */) {
-    v = wave_sum_f64(v);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((red[0] + red[1]) + red[2]) + red[3];
-}
-
 // One element: the three fp32 roundings of the gradient term (difference, product, FMA) and the fp64 term of the value.
 // Products and sums stay separate operations (no contraction): the value is the sum of ROUNDED fp64 products.
 __device__ __forceinline__ float ewc_elem(float th, float an, float fi, float g, float w2, double &acc) {
@@ -101,7 +87,7 @@ __global__ __launch_bounds__(256) void ewc_kernel(const float *__restrict__ thet
 }
 
 // out[0] = sum of the partials: thread t adds partials[t], partials[t + 256], ... in ascending order, then the same butterfly and
-// wave order as above — a function of nblocks alone.
+// wave order (block_sum_256_f64, common.h) — a function of nblocks alone.
 __global__ __launch_bounds__(256) void ewc_finish_kernel(const double *__restrict__ partials, int64_t nblocks,
                                                          double *__restrict__ out) {
     __shared__ double red[4];

@@ -14,9 +14,8 @@ records; CUDA float32 images then take two fused HIP launches per direction (ric
 """
 import numpy as np
 import torch
-from torch.autograd import Function
 
-from .augment import ParamStaging, upload_params  # noqa: F401  (re-used: pinned double-buffered staging of parameter blocks)
+from .param_block import ParamStaging, fused_launch, linear_pair, upload_params  # noqa: F401  (ParamStaging: exported here too)
 
 __all__ = ['POLICIES', 'PARAM_DTYPE', 'parse_policy', 'shift_range', 'cut_size', 'cut_bounds', 'draw_params', 'identity_params',
            'check_params', 'apply_params', 'DiffAugFn', 'DiffAugAdjFn', 'diffaug_fused', 'diffaug']
@@ -128,54 +127,17 @@ def apply_params(img, params):
 
 
 # ------------------------------------------------------------------------------------------------------- fused path (HIP, host side)
-def _launch(entry, x, params, bias=True):
-    from ._lib import check, lib, ptr, require_cuda_f32, stream_ptr
-    require_cuda_f32(x)
-    x = x.contiguous()
-    n, c, h, w = x.shape
-    if c != 3 or not params.is_cuda or params.numel() * params.element_size() < n * PARAM_DTYPE.itemsize:
-        raise RuntimeError(f'diffaug: needs [N, 3, H, W] images and N parameter entries on the device; got {tuple(x.shape)}, '
-                           f'{params.numel() * params.element_size()} bytes')
+def _workspace(lib, n, h, w, device):
     nbytes = int(lib.rick_diffaug_workspace_bytes(n, h, w))
     if nbytes < 0:
-        raise RuntimeError(f'diffaug: unsupported image shape {tuple(x.shape)}')
-    ws = torch.empty(nbytes // 8, device=x.device, dtype=torch.float64)
-    y = torch.empty_like(x)
-    if entry == 'fwd':
-        check(lib.rick_diffaug_fwd_f32(ptr(x), ptr(params), ptr(ws), ptr(y), n, h, w, int(bias), stream_ptr()), 'rick_diffaug_fwd_f32')
-    else:
-        check(lib.rick_diffaug_adj_f32(ptr(x), ptr(params), ptr(ws), ptr(y), n, h, w, stream_ptr()), 'rick_diffaug_adj_f32')
-    return y
+        raise RuntimeError(f'diffaug: unsupported image shape {(n, 3, h, w)}')
+    return torch.empty(nbytes // 8, device=device, dtype=torch.float64)
 
 
-class DiffAugFn(Function):
-    """y = diffaug(x) for fixed per-image draws (`bias`: with the brightness offset).  Linear in x up to the offset: its backward is
-    DiffAugAdjFn, whose backward is this map without the offset — closed under differentiation to any order.  No gradient flows to
-    the parameters."""
-
-    @staticmethod
-    def forward(ctx, x, params, bias=True):
-        ctx.save_for_backward(params)
-        return _launch('fwd', x, params, bias=bias)
-
-    @staticmethod
-    def backward(ctx, gy):
-        (params,) = ctx.saved_tensors
-        return DiffAugAdjFn.apply(gy, params), None, None
-
-
-class DiffAugAdjFn(Function):
-    """gx = (linear part of diffaug)^T gy."""
-
-    @staticmethod
-    def forward(ctx, gy, params):
-        ctx.save_for_backward(params)
-        return _launch('adj', gy, params)
-
-    @staticmethod
-    def backward(ctx, gg):
-        (params,) = ctx.saved_tensors
-        return DiffAugFn.apply(gg, params, False), None
+# y = diffaug(x) for fixed per-image draws (`bias`: with the brightness offset) and the adjoint of its linear part, each the other's
+# backward; no gradient flows to the parameters.
+DiffAugFn, DiffAugAdjFn = linear_pair(fused_launch('diffaug', PARAM_DTYPE.itemsize, 'rick_diffaug', _workspace),
+                                      'DiffAugFn', 'DiffAugAdjFn')
 
 
 def diffaug_fused(img, params):

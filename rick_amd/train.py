@@ -19,8 +19,11 @@ from torch import autograd
 
 from . import op
 from ._lib import check, lib, ptr, stream_ptr
+from . import augment as A
+from . import diffaug as DA
 from .augment import augment_fused
 from .diffaug import diffaug_fused
+from .param_block import StepParamBlock
 
 
 # --------------------------------------------------------------------------- losses
@@ -401,6 +404,59 @@ class AdaController:
         return self.p
 
 
+class StepAugmenter:
+    """The discriminator-side augmentation of a trainer, ADA or DiffAugment (alternatives).  The recipes differ in two things:
+    `draw(batch)`, the host records of one reference call, and `apply(x, dev)`, the fused op on a device parameter block.  Shared:
+    `blocks`, the persistent parameter block of each step ('d', 'r1', 'g'; captured graphs read it), and `prepare`, the host side
+    of a step's augmentation that its `pre=` hook calls."""
+
+    def __init__(self, trainer):
+        self.tr, self.blocks = trainer, {}
+
+    def prepare(self, key, n_calls, batch, reverse=False):
+        """One draw per reference call, in the reference's order, uploaded into the step's block (created on the first, eager
+        call).  `n_calls` calls of `batch` images each; `reverse`: the launch's images are in the opposite order of the draws."""
+        blk = self.blocks.get(key)
+        if blk is None:
+            blk = self.blocks[key] = StepParamBlock(self.itemsize, n_calls * batch, self.tr.device, self.who)
+        return blk.fill([self.draw(batch) for _ in range(n_calls)], reverse)
+
+
+class AdaAugmenter(StepAugmenter):
+    """One (G, C) draw per call at the trainer's current p, or the trainer's `aug_source(n)` in the sampler's place."""
+    itemsize, who = A.PARAM_DTYPE.itemsize, 'augment'
+
+    def draw(self, batch):
+        tr, size = self.tr, self.tr.cfg.size
+        if tr.aug_source is not None:
+            G, C = tr.aug_source(batch)
+            G, pads = A.draw_affine(tr.ada.p, batch, size, size, G)
+        else:
+            G, pads = A.draw_affine(tr.ada.p, batch, size, size)
+            C = A.sample_color(tr.ada.p, batch)
+        return A.aug_params(G, C, size, size, pads)
+
+    def apply(self, x, dev):
+        return augment_fused(x, dev)
+
+
+class DiffAugmenter(StepAugmenter):
+    """The published trainer's draws of one call for the parsed policy, or the trainer's `diffaug_source(n)`, checked."""
+    itemsize, who = DA.PARAM_DTYPE.itemsize, 'diffaug'
+
+    def __init__(self, trainer, policy):
+        super().__init__(trainer)
+        self.policy = DA.parse_policy(policy)
+
+    def draw(self, batch):
+        tr, size = self.tr, self.tr.cfg.size
+        rec = tr.diffaug_source(batch) if tr.diffaug_source is not None else DA.draw_params(batch, size, size, self.policy)
+        return DA.check_params(rec, size, size)
+
+    def apply(self, x, dev):
+        return diffaug_fused(x, dev)
+
+
 def g_optim_filter(name):
     return 'convs' in name                              # train_dynamic_update_prune.py:909-911
 
@@ -418,11 +474,10 @@ class RickTrainer:
 
     def __init__(self, cfg, generator, discriminator, g_ema, d_ema, dp=None, g_source=None, ewc=None):
         self.cfg, self.g, self.d, self.g_ema, self.d_ema, self.dp = cfg, generator, discriminator, g_ema, d_ema, dp
-        # DiffAugment (cfg.diffaug): the parsed policy; the alternative to ADA on the discriminator side, never both
-        self._diffaug_policy = None
+        # the discriminator-side augmentation: DiffAugment (cfg.diffaug) or ADA (cfg.augment), never both; None when both are off
+        self._augmenter = AdaAugmenter(self) if cfg.augment else None
         if cfg.diffaug:
-            from .diffaug import parse_policy
-            self._diffaug_policy = parse_policy(cfg.diffaug)
+            self._augmenter = DiffAugmenter(self, cfg.diffaug)
             if cfg.augment:
                 raise ValueError('RickTrainer: augment (ADA) and diffaug are alternatives; set one of them')
         self.device = next(generator.parameters()).device
@@ -469,18 +524,13 @@ class RickTrainer:
         self._gs, self._inject, self._layer_idx, self._real = {}, {}, None, None
         self._fisher_state = None   # persistent accumulators / static inputs / captured per-sample graph of the Fisher sweep
         self._pending = None        # (graph state, flat, optimiser, optimiser graph) of a step whose gradient exchange is in flight
-        # adaptive discriminator augmentation (cfg.augment): p, the device sign sum of D's real logits, the persistent device
-        # parameter blocks of the D / G steps (captured graphs read them; the host refills them before each step) and the D
-        # step's augmented reals (the R1 step's input).  `aug_source(n)`, when set, returns the (G, C) of a call of n images
-        # instead of the sampler (tests pin the transforms with it).
+        # adaptive discriminator augmentation (cfg.augment): p, the device sign sum of D's real logits and the D step's augmented
+        # reals (`_aug_real`, the R1 step's input).  The persistent device parameter blocks of the steps are the augmenter's: each
+        # step's `pre=` hook refills its block, captured graphs read it.  `aug_source(n)`, when set, returns the (G, C) of a call of
+        # n images instead of the sampler, `diffaug_source(n)` DiffAugment's parameter records (tests pin the draws with them).
         self.ada = AdaController(cfg)
-        self.aug_source = None
-        self._aug = {}
+        self.aug_source = self.diffaug_source = None
         self._ada_sum = torch.zeros((), device=self.device) if cfg.augment and self.ada.adaptive else None
-        # DiffAugment: the persistent device parameter blocks of the D / R1 / G steps, refilled by each step's `pre=` hook.
-        # `diffaug_source(n)`, when set, returns the parameter records of a call of n images instead of the sampler (tests).
-        self.diffaug_source = None
-        self._daug = {}
         if dp is not None:
             dp.attach(self.g_flat, self.d_flat)
         # kernel modulation of the frozen filters (cfg.kml_rank > 0): one adapter per network, stepped with the network's lr / betas
@@ -838,46 +888,6 @@ class RickTrainer:
     def ada_p(self, v):
         self.ada.p = float(v)
 
-    def _aug_block(self, key, n_calls, batch, reverse=False):
-        """Host side of the augmentation of a step (its `pre=` hook): one (G, C) draw per reference call, in the reference's
-        order, uploaded into the step's persistent device parameter block.  `n_calls` calls of `batch` images each; `reverse`:
-        the launch's images are in the opposite order of the draws."""
-        from . import augment as A
-        ent = self._aug.get(key)
-        h, w = self.cfg.size, self.cfg.size
-        if ent is None:
-            ent = self._aug[key] = {'dev': torch.zeros(n_calls * batch * A.PARAM_DTYPE.itemsize, dtype=torch.uint8,
-                                                       device=self.device), 'staging': A.ParamStaging()}
-        blocks = []
-        for _ in range(n_calls):
-            if self.aug_source is not None:
-                G, C = self.aug_source(batch)
-                G, pads = A.draw_affine(self.ada.p, batch, h, w, G)
-            else:
-                G, pads = A.draw_affine(self.ada.p, batch, h, w)
-                C = A.sample_color(self.ada.p, batch)
-            blocks.append(A.aug_params(G, C, h, w, pads))
-        A.upload_params(np.concatenate(blocks[::-1] if reverse else blocks), self.device, dst=ent['dev'], staging=ent['staging'])
-        ent['calls'] = blocks
-        return ent
-
-    def _diffaug_block(self, key, n_calls, batch, reverse=False):
-        """Host side of DiffAugment in a step (its `pre=` hook), the mechanism of _aug_block: one draw per call of the published
-        trainer, in its order, checked and uploaded into the step's persistent device parameter block."""
-        from . import diffaug as DA
-        ent = self._daug.get(key)
-        h, w = self.cfg.size, self.cfg.size
-        if ent is None:
-            ent = self._daug[key] = {'dev': torch.zeros(n_calls * batch * DA.PARAM_DTYPE.itemsize, dtype=torch.uint8,
-                                                        device=self.device), 'staging': DA.ParamStaging()}
-        blocks = []
-        for _ in range(n_calls):
-            rec = self.diffaug_source(batch) if self.diffaug_source is not None else DA.draw_params(batch, h, w, self._diffaug_policy)
-            blocks.append(DA.check_params(rec, h, w))
-        DA.upload_params(np.concatenate(blocks[::-1] if reverse else blocks), self.device, dst=ent['dev'], staging=ent['staging'])
-        ent['calls'] = blocks
-        return ent
-
     def _ada_after_d_step(self, batch):
         """Adaptive p (train_dynamic_update_prune.py:440-459) after a D step of `batch` images on this rank."""
         if self._ada_sum is None:
@@ -897,8 +907,7 @@ class RickTrainer:
         key = 'd' if graph else None
         batch = real_img.shape[0]
 
-        aug = self.cfg.augment
-        daug = self._diffaug_policy is not None
+        aug, ada = self._augmenter, self.cfg.augment
 
         def fb():
             with torch.no_grad():
@@ -907,11 +916,10 @@ class RickTrainer:
                 else:
                     fake_img, _ = self.g(noise, noise=g_noise)
                 x = torch.cat([fake_img, real_img], 0)
-                if aug:                          # augment(real), augment(fake) of the reference: one launch pair
-                    x = augment_fused(x, self._aug['d']['dev'])
-                    self._aug_real.copy_(x[batch:])           # the R1 step's input (a static buffer under graphs)
-                if daug:                         # DiffAugment(real), DiffAugment(fake): one launch pair over cat(fake, real)
-                    x = diffaug_fused(x, self._daug['d']['dev'])
+                if aug:                          # augment(real), augment(fake) of the reference: one launch pair over cat(fake, real)
+                    x = aug.apply(x, aug.blocks['d'].dev)
+                    if ada:                      # the R1 step's input (a static buffer under graphs)
+                        self._aug_real.copy_(x[batch:])
             # one pass over cat(fake, real): identical to the reference's two calls (per-call minibatch-stddev
             # statistics are kept), half the launches and twice the GEMM rows per launch
             with self._sink():                   # conv weight gradients are added straight into the flat buffer
@@ -931,20 +939,18 @@ class RickTrainer:
             if graph:
                 self._draw_inject(key)
             if aug:
-                if getattr(self, '_aug_real', None) is None or self._aug_real.shape != real_img.shape:
+                if ada and (getattr(self, '_aug_real', None) is None or self._aug_real.shape != real_img.shape):
                     self._aug_real = torch.empty_like(real_img)
-                # the reference draws real's (G, C) first, then fake's; the launch runs over cat(fake, real)
-                self._aug_block('d', 2, batch, reverse=True)
-            if daug:                             # the same order: real's draws first, the launch over cat(fake, real)
-                self._diffaug_block('d', 2, batch, reverse=True)
-        self._run(key, fb, self.d_flat, self.d_optim, pre=pre if (graph or aug or daug) else None)
+                # the reference draws real's parameters first, then fake's; the launch runs over cat(fake, real)
+                aug.prepare('d', 2, batch, reverse=True)
+        self._run(key, fb, self.d_flat, self.d_optim, pre=pre if (graph or aug) else None)
         self._ada_after_d_step(batch)
         return self.losses['d']
 
     def r1_step(self, real_img, i=10 ** 9, graph=False):
         cfg = self.cfg
         self._set_d_stage(i)
-        daug = self._diffaug_policy is not None
+        aug = None if cfg.augment else self._augmenter          # ADA: the caller passes the D step's augmented reals (_aug_real)
         batch = real_img.shape[0]
 
         def fb():
@@ -953,14 +959,14 @@ class RickTrainer:
                 # DiffAugment (the convention of its authors' StyleGAN2 trainer): D sees a fresh draw of the augmented reals, the
                 # penalty is on the gradient w.r.t. the PLAIN reals — adjoint in the inner gradient, forward without offset in its
                 # backward
-                real_pred, _ = self.d(diffaug_fused(real, self._daug['r1']['dev']) if daug else real)
+                real_pred, _ = self.d(aug.apply(real, aug.blocks['r1'].dev) if aug else real)
                 real_pred = real_pred.view(real.size(0), -1).mean(dim=1).unsqueeze(1)
                 r1_loss = d_r1_loss(real_pred, real)
                 self._zero_grad(self.d_flat)
                 (cfg.r1 / 2 * r1_loss * cfg.d_reg_every + 0 * real_pred[0]).backward()
             self.losses['r1'] = r1_loss.detach()
         self._run('r1' if graph else None, fb, self.d_flat, self.d_optim,
-                  pre=(lambda: self._diffaug_block('r1', 1, batch)) if daug else None)
+                  pre=(lambda: aug.prepare('r1', 1, batch)) if aug else None)
         return self.losses['r1']
 
     def _feature_pair(self, z, g_noise=None):
@@ -1003,16 +1009,13 @@ class RickTrainer:
                 else:
                     box['fake'], _ = self.g(noise, noise=g_noise)
 
-        aug = self.cfg.augment
-        daug = self._diffaug_policy is not None
+        aug = self._augmenter
 
         def fb():
             with self._sink(), self._d_frozen():
                 fake = box.pop('fake')
-                if aug:
-                    fake = augment_fused(fake, self._aug['g']['dev'])
-                if daug:                         # with gradients: the adjoint carries them back to G
-                    fake = diffaug_fused(fake, self._daug['g']['dev'])
+                if aug:                          # with gradients: the adjoint carries them back to G
+                    fake = aug.apply(fake, aug.blocks['g'].dev)
                 fake_pred, _ = self.d(fake)
                 g_loss = g_nonsaturating_loss(fake_pred)
                 total = g_loss
@@ -1028,9 +1031,7 @@ class RickTrainer:
             if graph:
                 self._draw_inject(key)
             if aug:
-                self._aug_block('g', 1, batch)
-            if daug:
-                self._diffaug_block('g', 1, batch)
+                aug.prepare('g', 1, batch)
         # the EWC term is added at the top of the optimiser step: after the gradient exchange (the eager data-parallel mode still
         # has bucket all-reduces in flight when backward() returns), in the G step only (the path-length step has its own
         # optimiser step: the term there would be weighted 1 + 1 / g_reg_every times)
@@ -1039,7 +1040,7 @@ class RickTrainer:
                 raise ValueError('RickTrainer: ewc_weight > 0 needs the anchor (set_ewc)')
             self.g_optim.before_step = self._ewc_term
         try:
-            self._run(key, fb, self.g_flat, self.g_optim, pre=pre if (graph or aug or daug) else None, fb_head=head)
+            self._run(key, fb, self.g_flat, self.g_optim, pre=pre if (graph or aug) else None, fb_head=head)
         finally:
             self.g_optim.before_step = None
         return self.losses['g']

@@ -215,7 +215,7 @@ def test_augmentation_off_leaves_the_trainer_as_it_was():
             tr.plr_step(None, pl_noise=pl_noise, g_noise=noises, graph=True)
             tr.ema_step()
         torch.cuda.synchronize()
-        assert tr._aug == {} and tr._ada_sum is None and getattr(tr, '_aug_real', None) is None
+        assert tr._augmenter is None and tr._ada_sum is None and getattr(tr, '_aug_real', None) is None
         return tr
     a, b = run(), run(augment_p=0.7, ada_target=0.2, ada_length=10)
     for fa, fb in ((a.g_flat, b.g_flat), (a.d_flat, b.d_flat), (a.g_ema_flat, b.g_ema_flat), (a.d_ema_flat, b.d_ema_flat)):

@@ -130,7 +130,7 @@ def test_diffaug_off_leaves_the_trainer_as_it_was():
         tr = RickTrainer(TrainConfig(size=size, batch=B, warmup_iter=0, **kw), g, d, *build(size))
         noises = [getattr(tr.g.noises, f'noise_{i}') for i in range(tr.g.num_layers)]
         out = [tr.d_step(real, [z], g_noise=noises).clone(), tr.r1_step(real).clone(), tr.g_step([z], g_noise=noises).clone()]
-        assert tr._daug == {} and tr._diffaug_policy is None
+        assert tr._augmenter is None            # no policy, and with it no parameter block of any step
         return tr, out
     (a, la), (b, lb) = run(), run(diffaug='')
     assert all(torch.equal(x, y) for x, y in zip(la, lb))
