@@ -707,10 +707,27 @@ int rick_fc_f32(const float *x, const float *wpk, const float *bias, float *ws, 
  * rick_rowmix_f32: y[k][t] = sum_m A[k][m] x[m][t], A [B][B] fp32 in device memory, y laid out like x (y != x).  Per element
  *   one fp32 chain A[k][0] x[0][t], then fma(A[k][m], x[m][t], .) for m = 1 .. B - 1: with A = I it returns x (finite values;
  *   -0 may come back as +0).  Reads B rows, writes B rows.
+ * rick_xgram_f32 (rick_amd/dcl.py): the same for two row sets in separate allocations, a [Ba][n] and b [Bb][n] (1 <= Ba, Bb <= 8,
+ *   both at row stride n, both in one memory layout): C [Ba][Bb] = <a_i, b_j>, na [Ba] = <a_i, a_i>, nb [Bb] = <b_j, b_j>, all
+ *   fp64 (device), from ONE pass over both operands.  Slices, element -> thread map, fma chain order, butterfly, wave order and
+ *   the ascending fp64 sum of the slices are rick_gram_f32's, so every entry is bit-identical to the entry rick_gram_f32 gives
+ *   for the same two rows (C[i][j] = G[i][Ba + j] of the rows stacked) and depends on its two rows alone.  ws holds
+ *   rick_xgram_workspace_bytes(Ba, Bb, n) bytes (-1 for sizes out of range).  16-byte loads only when a % 16 == 0, b % 16 == 0
+ *   and n % 4 == 0; otherwise both operands are read element by element (the same sums).
+ * rick_xrowmix_f32: its adjoint, y[k][t] = d[k] a[k][t] + sum_m M[k][m] b[m][t], M [Ba][Bb] and d [Ba] fp32 in device memory,
+ *   y [Ba][n] laid out like a and overlapping neither a nor b.  Per element one fp32 chain d[k] a[k][t], then
+ *   fma(M[k][m], b[m][t], .) for m = 0 .. Bb - 1: with M = 0, d = 1 it returns a, with d = 0 and M one-hot that row of b (finite
+ *   values; -0 may come back as +0).  dA = gC B + 2 diag(gna) A is one call; dB the same call with the roles swapped and gC^T.
+ * Both return RICK_EINVAL on null or misaligned pointers (4 bytes; 8 for the fp64 outputs), sizes out of range, or y aliasing.
  * No atomics, no host synchronisation, no allocation; every launch is on `stream` and can be captured. */
 int64_t rick_gram_workspace_bytes(int B, int64_t n);
 int rick_gram_f32(const float *x, int B, int64_t n, void *ws, double *G, void *stream);
 int rick_rowmix_f32(const float *A, const float *x, float *y, int B, int64_t n, void *stream);
+int64_t rick_xgram_workspace_bytes(int Ba, int Bb, int64_t n);
+int rick_xgram_f32(const float *a, int Ba, const float *b, int Bb, int64_t n, void *ws, double *C, double *na, double *nb,
+                   void *stream);
+int rick_xrowmix_f32(const float *M, const float *d, const float *a, const float *b, float *y, int Ba, int Bb, int64_t n,
+                     void *stream);
 
 /* ---------------------------------------------------------------------------------------
  * EWC — the elastic-weight-consolidation penalty on the flat parameter buffers (rick_amd/ewc.py):

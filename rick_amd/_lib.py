@@ -200,6 +200,9 @@ SIGNATURES = {
     'rick_gram_workspace_bytes': (c_i64, [c_int, c_i64]),
     'rick_gram_f32': (c_int, [c_fp, c_int, c_i64, c_fp, c_fp, c_fp]),
     'rick_rowmix_f32': (c_int, [c_fp, c_fp, c_fp, c_int, c_i64, c_fp]),
+    'rick_xgram_workspace_bytes': (c_i64, [c_int, c_int, c_i64]),
+    'rick_xgram_f32': (c_int, [c_fp, c_int, c_fp, c_int, c_i64, c_fp, c_fp, c_fp, c_fp, c_fp]),
+    'rick_xrowmix_f32': (c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_i64, c_fp]),
     'rick_ewc_blocks': (c_i64, [c_i64]),
     'rick_ewc_f32': (c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, c_i64, c_f, c_fp, c_fp]),
     'rick_ewc_finish_f64': (c_int, [c_fp, c_i64, c_fp, c_fp]),

@@ -94,6 +94,7 @@ class EqualLinear(nn.Module):
 
     def forward(self, x, pixelnorm=False):
         if (x.ndim == 2 and x.is_cuda and x.dtype == torch.float32 and x.shape[0] <= 16 and x.shape[1] % 4 == 0
+                and x.shape[0] * x.shape[1] * 4 <= 160 * 1024      # the kernel keeps x in LDS (a no-grad D pass of > 5 images: 8192 wide)
                 and self.activation in (None, 'fused_lrelu') and self._no_grad_needed(x)):
             # short-batch forward without autograd (the mapping network of every train step): one launch for
             # [PixelNorm +] GEMM + bias * lr_mul + activation instead of 3 (+ 5)

@@ -371,6 +371,10 @@ class TrainConfig:
     ewc_weight: float = 0.0                          # elastic weight consolidation on the generator (rick_amd/ewc.py): the paper's 5e8
     kml_rank: int = 0                                # kernel modulation of the frozen filters (rick_amd/kml.py): AdAM's rank, 1 ... 8
     diffaug: str = ''                                # DiffAugment policy (rick_amd/diffaug.py), e.g. 'color,translation,cutout'; '' = off
+    dcl_g_weight: float = 0.0                        # DCL's generator contrastive term CL1 (rick_amd/dcl.py): lambda1, recalled as 2 (unverified)
+    dcl_d_weight: float = 0.0                        # DCL's discriminator contrastive term CL2: lambda2, recalled as 0.5 (unverified)
+    dcl_tau: float = 0.07                            # the temperature of both terms
+    dcl_batch: int = 4                               # CL1's own latent batch (like cdc_batch)
 
 
 class AdaController:
@@ -468,11 +472,13 @@ def d_optim_filter(name):
 class RickTrainer:
     """One process / one GPU worth of the adaptation loop.  `dp` (rick_amd.dist.DataParallelGrads
     or None) averages flat gradients over ranks with RCCL before each optimiser step.  `g_source`: the frozen source
-    generator of the distance-consistency term (required when cfg.cdc_weight > 0; put in eval mode, gradients off).  `ewc`: the
+    generator of the distance-consistency term and of the dual contrastive terms (required when cfg.cdc_weight, cfg.dcl_g_weight
+    or cfg.dcl_d_weight > 0; put in eval mode, gradients off); `d_source`: the frozen source discriminator of the discriminator
+    contrastive term (required when cfg.dcl_d_weight > 0; treated like g_source).  `ewc`: the
     anchor of the elastic-weight-consolidation term (required when cfg.ewc_weight > 0), given as what `set_ewc` takes: a pair
     (source_state, fisher) of {name: tensor} mappings, fisher None for the L2-SP penalty."""
 
-    def __init__(self, cfg, generator, discriminator, g_ema, d_ema, dp=None, g_source=None, ewc=None):
+    def __init__(self, cfg, generator, discriminator, g_ema, d_ema, dp=None, g_source=None, ewc=None, d_source=None):
         self.cfg, self.g, self.d, self.g_ema, self.d_ema, self.dp = cfg, generator, discriminator, g_ema, d_ema, dp
         # the discriminator-side augmentation: DiffAugment (cfg.diffaug) or ADA (cfg.augment), never both; None when both are off
         self._augmenter = AdaAugmenter(self) if cfg.augment else None
@@ -481,7 +487,7 @@ class RickTrainer:
             if cfg.augment:
                 raise ValueError('RickTrainer: augment (ADA) and diffaug are alternatives; set one of them')
         self.device = next(generator.parameters()).device
-        self.g_source = g_source
+        self.g_source, self.d_source = g_source, d_source
         if cfg.cdc_weight < 0 or (cfg.cdc_weight > 0 and cfg.cdc_batch < 2):
             raise ValueError('RickTrainer: cdc_weight must be >= 0 and cdc_batch >= 2')
         if cfg.ewc_weight < 0 or not math.isfinite(cfg.ewc_weight):
@@ -492,13 +498,27 @@ class RickTrainer:
             raise ValueError('RickTrainer: cdc_weight > 0 needs the frozen source generator (g_source=)')
         if isinstance(cfg.kml_rank, bool) or not isinstance(cfg.kml_rank, int) or not 0 <= cfg.kml_rank <= 8:
             raise ValueError('RickTrainer: kml_rank must be an integer in 0 ... 8')
-        if g_source is not None:
-            if g_source is generator:
-                raise ValueError('RickTrainer: g_source must be a copy of the source generator, not the generator being trained')
-            if next(g_source.parameters()).device != self.device:
-                raise ValueError(f'RickTrainer: g_source on {next(g_source.parameters()).device}, generator on {self.device}')
-            g_source.eval()
-            for p in g_source.parameters():
+        for w in (cfg.dcl_g_weight, cfg.dcl_d_weight):
+            if w < 0 or not math.isfinite(w):
+                raise ValueError('RickTrainer: dcl_g_weight and dcl_d_weight must be finite and >= 0')
+        if not cfg.dcl_tau > 0 or not math.isfinite(cfg.dcl_tau) or cfg.dcl_batch < 1:
+            raise ValueError('RickTrainer: dcl_tau must be > 0 and dcl_batch >= 1')
+        if cfg.dcl_g_weight > 0 and g_source is None:
+            raise ValueError('RickTrainer: dcl_g_weight > 0 needs the frozen source generator (g_source=)')
+        if cfg.dcl_d_weight > 0 and (g_source is None or d_source is None):
+            raise ValueError('RickTrainer: dcl_d_weight > 0 needs the frozen source generator and discriminator (g_source=, d_source=)')
+        if cfg.dcl_d_weight > 0 and (cfg.augment or cfg.diffaug):
+            raise ValueError('RickTrainer: dcl_d_weight > 0 together with augment or diffaug is not supported (the source-side image '
+                             "would have to be augmented with the fake's draw)")
+        for name, src, net in (('g_source', g_source, generator), ('d_source', d_source, discriminator)):
+            if src is None:
+                continue
+            if src is net:
+                raise ValueError(f'RickTrainer: {name} must be a copy of the source network, not the network being trained')
+            if next(src.parameters()).device != self.device:
+                raise ValueError(f'RickTrainer: {name} on {next(src.parameters()).device}, generator on {self.device}')
+            src.eval()
+            for p in src.parameters():
                 p.requires_grad = False
         # packed conv weights: one refresh launch per network
         self._pack_groups = [op.register_pack_group(net) for net in (generator, discriminator)]
@@ -902,8 +922,19 @@ class RickTrainer:
         self._ada_sum.zero_()
 
     # ---- steps (each returns the loss tensor; no host sync)
-    def d_step(self, real_img, noise, i=10 ** 9, g_noise=None, graph=False):
+    def d_step(self, real_img, noise, i=10 ** 9, g_noise=None, graph=False, dcl_layers=None, dcl_inject=None):
+        """Logistic D step.  With cfg.dcl_d_weight > 0 the discriminator contrastive term (rick_amd/dcl.py) is added before the one
+        backward(): anchors and negatives are the two halves of the feature list the pass over cat(fake, real) returns anyway, the
+        positives come from one no-grad pass G_s -> D_s with the mixing index and noise maps of the fakes (drawn here, handed to
+        both generators).  Its drawn layers change the launch list, so such a step is never captured: `graph=True` then runs the
+        eager path, as g_step does with the distance-consistency term.  `dcl_layers` and `dcl_inject` fix the draws (tests);
+        `g_noise` fixes the noise maps."""
         self._set_d_stage(i)
+        dcl_on = self.cfg.dcl_d_weight > 0
+        if dcl_on and graph:
+            graph = False
+            if noise is None:
+                noise = mixing_noise(real_img.shape[0], self.cfg.latent, self.cfg.mixing, self.device)
         key = 'd' if graph else None
         batch = real_img.shape[0]
 
@@ -913,6 +944,10 @@ class RickTrainer:
             with torch.no_grad():
                 if graph:
                     fake_img, _ = self.g([self._graph_latents(key, batch)], input_is_latent=True, noise=g_noise)
+                elif dcl_on:
+                    inject, maps = self._dcl_d_draws(noise, g_noise, dcl_inject)
+                    fake_img, _ = self.g(noise, noise=maps, inject_index=inject)
+                    feats_pos = self.d_source(self.g_source(noise, noise=maps, inject_index=inject)[0])[1]
                 else:
                     fake_img, _ = self.g(noise, noise=g_noise)
                 x = torch.cat([fake_img, real_img], 0)
@@ -923,16 +958,25 @@ class RickTrainer:
             # one pass over cat(fake, real): identical to the reference's two calls (per-call minibatch-stddev
             # statistics are kept), half the launches and twice the GEMM rows per launch
             with self._sink():                   # conv weight gradients are added straight into the flat buffer
-                pred, _ = self.d(x, calls=2)
+                pred, feats = self.d(x, calls=2)
                 fake_pred, real_pred = pred.chunk(2, 0)
                 d_loss = d_logistic_loss(real_pred, fake_pred)
+                total = d_loss
+                if dcl_on:
+                    from . import dcl
+                    nf = fake_img.shape[0]
+                    layers = dcl_layers if dcl_layers is not None else dcl.draw_d_layers(len(feats), nf)
+                    dcl_loss = dcl.discriminator_contrastive_loss([f[:nf] for f in feats], feats_pos, [f[nf:] for f in feats],
+                                                                  layers, self.cfg.dcl_tau)
+                    total = d_loss + self.cfg.dcl_d_weight * dcl_loss
+                    self.losses['dcl_d'] = dcl_loss.detach()
                 if self._ada_sum is not None:
                     self._ada_sum.add_(torch.sign(real_pred.detach()).sum())
                 self._zero_grad(self.d_flat)
                 # bias / noise-strength sums: one second-stage launch for the whole pass; (RICK_WGRAD_OVERLAP=1: sunk weight
                 # gradients on a second stream next to the data-gradient chain — measured slower, off by default, op/conv.py)
                 with op.deferred_sums(), op.wgrad_overlap():
-                    d_loss.backward()
+                    total.backward()
             self.losses.update(d=d_loss.detach(), real_score=real_pred.detach().mean(), fake_score=fake_pred.detach().mean())
 
         def pre():
@@ -988,13 +1032,69 @@ class RickTrainer:
         feats_t, feats_s = self._feature_pair(z, g_noise)
         return cdc.distance_consistency_loss(feats_t, feats_s, layers)
 
-    def g_step(self, noise, g_noise=None, graph=False, cdc_noise=None, cdc_layers=None):
+    def _dcl_d_draws(self, noise, g_noise, inject=None):
+        """The draws Generator.forward would make for the fakes of a D step, made here so that the generator being trained and the
+        frozen source generator get the same ones: the style-mixing index (None for a single latent) and the noise maps."""
+        if len(noise) < 2:
+            inject = None
+        elif inject is None:
+            inject = random.randint(1, self.g.n_latent - 1)
+        if g_noise is None:
+            B = noise[0].shape[0]
+            res = [4] + [2 ** k for k in range(3, self.g.log_size + 1) for _ in range(2)]
+            flat = torch.empty(B * sum(r * r for r in res), device=self.device, dtype=torch.float32).normal_()
+            g_noise, o = [], 0
+            for r in res:
+                g_noise.append(flat[o:o + B * r * r].view(B, 1, r, r))
+                o += B * r * r
+        return inject, g_noise
+
+    def _dcl_g_term(self, dcl_noise=None, dcl_layers=None, g_noise=None, pair=None):
+        """The unweighted generator contrastive loss CL1 (rick_amd/dcl.py) of one draw: z ~ N(0, I) [dcl_batch, latent] through
+        the frozen source generator (no grad) and the generator being trained, one drawn feature layer per sample.  `pair`: a
+        forward pair (feats_t, feats_s) to use instead of making one (the distance-consistency term's, when the batches agree)."""
+        from . import cdc, dcl
+        cfg = self.cfg
+        if pair is None:
+            z = dcl_noise if dcl_noise is not None else torch.randn(cfg.dcl_batch, cfg.latent, device=self.device)
+            pair = self._feature_pair(z, g_noise)
+        feats_t, feats_s = pair
+        layers = dcl_layers if dcl_layers is not None else cdc.draw_layers(self.g.n_latent, feats_t[0].shape[0])
+        return dcl.generator_contrastive_loss(feats_t, feats_s, layers, cfg.dcl_tau)
+
+    def _consistency_terms(self, cdc_noise=None, cdc_layers=None, dcl_noise=None, dcl_layers=None, g_noise=None):
+        """The unweighted feature-consistency terms of a G step that are switched on, {'cdc': ..., 'dcl_g': ...}.  With both on and
+        equal batches they share ONE forward pair (the latents are cdc_noise, else dcl_noise, else drawn); otherwise each makes
+        its own."""
+        from . import cdc
+        cfg, out = self.cfg, {}
+        cdc_on, dcl_on = cfg.cdc_weight > 0, cfg.dcl_g_weight > 0
+        nc = cdc_noise.shape[0] if cdc_noise is not None else cfg.cdc_batch
+        nd = dcl_noise.shape[0] if dcl_noise is not None else cfg.dcl_batch
+        if cdc_on and dcl_on and nc == nd and (cdc_noise is None or dcl_noise is None or cdc_noise is dcl_noise):
+            z = cdc_noise if cdc_noise is not None else dcl_noise
+            if z is None:
+                z = torch.randn(nc, cfg.latent, device=self.device)
+            pair = self._feature_pair(z, g_noise)
+            layers = cdc_layers if cdc_layers is not None else cdc.draw_layers(self.g.n_latent, nc)
+            out['cdc'] = cdc.distance_consistency_loss(pair[0], pair[1], layers)
+            out['dcl_g'] = self._dcl_g_term(dcl_layers=dcl_layers, pair=pair)
+            return out
+        if cdc_on:
+            out['cdc'] = self._cdc_term(cdc_noise, cdc_layers, g_noise)
+        if dcl_on:
+            out['dcl_g'] = self._dcl_g_term(dcl_noise, dcl_layers, g_noise)
+        return out
+
+    def g_step(self, noise, g_noise=None, graph=False, cdc_noise=None, cdc_layers=None, dcl_noise=None, dcl_layers=None):
         """Non-saturating G step.  With cfg.cdc_weight > 0 the distance-consistency term is added before the one backward():
         its drawn layers change the launch list from step to step, so such a step is never captured — `graph=True` then runs
         the eager path (its own mixing noise, no step graph) while every other step type keeps replaying.  `cdc_noise`
-        [cdc_batch, latent] and `cdc_layers` fix the term's draws (tests); `g_noise` also fixes its noise maps."""
+        [cdc_batch, latent] and `cdc_layers` fix the term's draws (tests); `g_noise` also fixes its noise maps.  The generator
+        contrastive term (cfg.dcl_g_weight > 0, `dcl_noise` / `dcl_layers`) is treated the same way."""
         cdc_on = self.cfg.cdc_weight > 0
-        if cdc_on and graph:
+        dcl_on = self.cfg.dcl_g_weight > 0
+        if (cdc_on or dcl_on) and graph:
             graph = False
             if noise is None:
                 noise = mixing_noise(self.cfg.batch, self.cfg.latent, self.cfg.mixing, self.device)
@@ -1019,10 +1119,16 @@ class RickTrainer:
                 fake_pred, _ = self.d(fake)
                 g_loss = g_nonsaturating_loss(fake_pred)
                 total = g_loss
-                if cdc_on:
+                if cdc_on and not dcl_on:
                     cdc_loss = self._cdc_term(cdc_noise, cdc_layers, g_noise)
                     total = g_loss + self.cfg.cdc_weight * cdc_loss
                     self.losses['cdc'] = cdc_loss.detach()
+                elif dcl_on:
+                    terms = self._consistency_terms(cdc_noise, cdc_layers, dcl_noise, dcl_layers, g_noise)
+                    for name, weight in (('cdc', self.cfg.cdc_weight), ('dcl_g', self.cfg.dcl_g_weight)):
+                        if name in terms:
+                            total = total + weight * terms[name]
+                            self.losses[name] = terms[name].detach()
                 self._zero_grad(self.g_flat)
                 with op.deferred_sums(), op.wgrad_overlap():
                     total.backward()

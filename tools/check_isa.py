@@ -25,7 +25,8 @@ PACKED = re.compile(r'^\s*(v_pk_fma_f32|v_pk_mul_f32|v_pk_add_f32)\b')
 CROSS = re.compile(r'^\s*(ds_bpermute_b32|ds_permute_b32|ds_swizzle_b32|v_permlane\w*|v_readlane_b32|v_writelane_b32|v_\w+_dpp)\b')
 # kernels whose cross-lane sums were wrong in the packed form, or share its pattern (LDS-broadcast operand x FMA chain -> wave sum)
 NO_PACKING = {'modulation.hip': ['modbank_fwd_kernel'], 'linear.hip': ['linear_fwd_kernel', 'linear_dgrad_kernel', 'linear_wgrad_kernel'],
-              'lpips.hip': ['lp_invnorm_kernel', 'lp_pair_kernel'], 'gram.hip': ['gram_kernel'], 'kml.hip': ['kml_grad_kernel']}
+              'lpips.hip': ['lp_invnorm_kernel', 'lp_pair_kernel'], 'gram.hip': ['gram_kernel', 'xgram_kernel'],
+              'kml.hip': ['kml_grad_kernel']}
 
 
 PER_FILE = {'linear.hip': ['-fno-slp-vectorize'], 'lpips.hip': ['-fno-slp-vectorize'], 'gram.hip': ['-fno-slp-vectorize'],
