@@ -845,6 +845,58 @@ int rick_diffaug_fwd_f32(const float *x, const rick_diffaug_param *params, void 
                          void *stream);
 int rick_diffaug_adj_f32(const float *gy, const rick_diffaug_param *params, void *ws, float *gx, int N, int H, int W, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * SVD — FSGAN's singular-value adaptation (rick_amd/svd.py).  A layer's weight is viewed as W[co][ci][taps] (tap innermost).  For
+ * every tap t the fp32 factors U[t][co][r] and Vt[t][r][ci], r = min(co, ci), of the source weight are frozen; the shift d[t][r] of
+ * the singular values is learnt on top of a snapshot W0:
+ *   W^[o,i,t] = W0[o,i,t] + sum_k (U[t,o,k] d[t,k]) Vt[t,k,i]         dd[t,k] = sum_o sum_i U[t,o,k] G[o,i,t] Vt[t,k,i]
+ * W (the optimised slice of the flat parameter buffer), W0 and G (the flat gradient) are n floats in ONE layout; every U lies in
+ * one buffer of nu floats, every Vt in one of nvt, every d in one of nd (dd at the same offsets in a buffer of its own).  All layers
+ * of a network go in one launch, driven by tables the host builds once:
+ *   layers[nlayers]    rick_svd_layer, below — in DEVICE memory for the kernels and the same bytes in HOST memory (layers_host)
+ *                      for the entry points, which validate every record before anything is launched
+ *   blocks[2 nblocks]  pairs (layer, tile) in device memory; a layer has rick_svd_apply_tiles() / rick_svd_grad_tiles() tiles,
+ *                      numbered from 0, and the list holds each of them once: nblocks = their sum over the table
+ * Products run on v_mfma_f32_32x32x2_f32: exact fp32 products, one fp32 fma chain per output element.
+ * rick_svd_apply_f32: a block takes rows [32 a, 32 a + 32) x columns [32 s b, 32 s (b + 1)) of a layer with ALL its taps
+ *   (s = 1 for taps >= 3, 2 for taps = 2, 4 for taps = 1; tile = a * ceil(ci / 32 s) + b).  The operand U[o,k] d[k] is rounded to
+ *   fp32 once (while a wave turns its 32 x 16 chunk of U through LDS), k ascends from 0 to r - 1, the epilogue adds W0 and stores;
+ *   the per-tap tiles are transposed through LDS so that
+ *   each row's run of columns x taps floats is stored contiguously.  d = 0 returns W0 bit for bit.  Nothing outside the layers
+ *   is written.
+ * rick_svd_grad_f32 + rick_svd_grad_finish_f32: a block takes directions [32 s a, 32 s (a + 1)) x columns [32 b, 32 b + 32) with
+ *   ALL taps (tile = a * ceil(ci / 32) + b): T[k,i] = sum_o U[t,o,k] G[o,i,t] with o ascending from 0 to co - 1, G staged in LDS
+ *   32 rows at a time as the contiguous run it is in memory; then T[k,i] Vt[t,k,i], the 32 columns added by the 16, 8, 4, 2, 1 xor
+ *   butterfly, into partials[part_off + (t r + k) ceil(ci / 32) + b].  T is never stored.  The finish launch adds the partials of
+ *   (t, k) in ascending b into dd[d_off + t r + k].
+ * Every summation order is a function of (co, ci, taps) alone: a layer's result does not depend on its place in the table, on
+ * addresses or on the other layers, and is bit-identical from run to run.  Rows and columns beyond co, ci and r enter as zeros by
+ * selection (clamped address inside the layer, value replaced).  No atomics, no allocation, no host synchronisation, one stream.
+ * RICK_EINVAL, with nothing launched, for: a null or misaligned pointer; a data or table pointer that is not device memory; a
+ * record with co, ci or taps < 1, taps > 16, r != min(co, ci), or an offset + extent past n / nu / nvt / nd / npart
+ * (rick_svd_check_table, also exported); a block count that is not the table's tile count; w == w0. */
+typedef struct {
+    int64_t off;              /* first element of the layer's weight in w / w0 / grad */
+    int64_t u_off, vt_off;    /* first element of U[taps][co][r] / Vt[taps][r][ci] */
+    int64_t d_off;            /* first element of d[taps][r] (dd at the same offset) */
+    int64_t part_off;         /* first float of the layer's partials: taps x r x ceil(ci / 32) = rick_svd_partials() */
+    int32_t co, ci, taps, r;
+    int32_t pad[2];
+} rick_svd_layer;             /* 64 B */
+int rick_svd_apply_tiles(int co, int ci, int taps);
+int rick_svd_grad_tiles(int co, int ci, int taps);
+int64_t rick_svd_partials(int co, int ci, int taps);
+int rick_svd_check_table(const rick_svd_layer *layers_host, int nlayers, int64_t n, int64_t nu, int64_t nvt, int64_t nd,
+                         int64_t npart);
+int rick_svd_apply_f32(const float *w0, float *w, int64_t n, const float *u, int64_t nu, const float *vt, int64_t nvt,
+                       const float *d, int64_t nd, const rick_svd_layer *layers, const rick_svd_layer *layers_host, int nlayers,
+                       const int32_t *blocks, int nblocks, void *stream);
+int rick_svd_grad_f32(const float *grad, int64_t n, const float *u, int64_t nu, const float *vt, int64_t nvt, float *partials,
+                      int64_t npart, const rick_svd_layer *layers, const rick_svd_layer *layers_host, int nlayers,
+                      const int32_t *blocks, int nblocks, void *stream);
+int rick_svd_grad_finish_f32(const float *partials, int64_t npart, float *dd, int64_t nd, const rick_svd_layer *layers,
+                             const rick_svd_layer *layers_host, int nlayers, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

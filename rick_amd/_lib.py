@@ -72,6 +72,12 @@ class KmlLayer(ctypes.Structure):
                 ('rows_off', c_int), ('nrows', c_int), ('rg', c_int), ('ngroups', c_int), ('flags_off', c_int)]
 
 
+class SvdLayer(ctypes.Structure):
+    """rick_svd_layer (include/rick_hip.h)."""
+    _fields_ = [('off', c_i64), ('u_off', c_i64), ('vt_off', c_i64), ('d_off', c_i64), ('part_off', c_i64), ('co', c_int),
+                ('ci', c_int), ('taps', c_int), ('r', c_int), ('pad', c_int * 2)]
+
+
 # name -> (restype, argtypes); every symbol declared in include/rick_hip.h
 SIGNATURES = {
     'rick_abi_version': (c_int, []),
@@ -215,6 +221,13 @@ SIGNATURES = {
     'rick_diffaug_check_params': (c_int, [c_fp, c_int, c_int, c_int]),
     'rick_diffaug_fwd_f32': (c_int, [c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, c_fp]),
     'rick_diffaug_adj_f32': (c_int, [c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_fp]),
+    'rick_svd_apply_tiles': (c_int, [c_int, c_int, c_int]),
+    'rick_svd_grad_tiles': (c_int, [c_int, c_int, c_int]),
+    'rick_svd_partials': (c_i64, [c_int, c_int, c_int]),
+    'rick_svd_check_table': (c_int, [c_fp, c_int, c_i64, c_i64, c_i64, c_i64, c_i64]),
+    'rick_svd_apply_f32': (c_int, [c_fp, c_fp, c_i64, c_fp, c_i64, c_fp, c_i64, c_fp, c_i64, c_fp, c_fp, c_int, c_fp, c_int, c_fp]),
+    'rick_svd_grad_f32': (c_int, [c_fp, c_i64, c_fp, c_i64, c_fp, c_i64, c_fp, c_i64, c_fp, c_fp, c_int, c_fp, c_int, c_fp]),
+    'rick_svd_grad_finish_f32': (c_int, [c_fp, c_i64, c_fp, c_i64, c_fp, c_fp, c_int, c_fp]),
 }
 
 if not os.path.exists(LIB_PATH):

@@ -375,6 +375,8 @@ class TrainConfig:
     dcl_d_weight: float = 0.0                        # DCL's discriminator contrastive term CL2: lambda2, recalled as 0.5 (unverified)
     dcl_tau: float = 0.07                            # the temperature of both terms
     dcl_batch: int = 4                               # CL1's own latent batch (like cdc_batch)
+    svd_adapt: bool = False                          # FSGAN's singular-value adaptation of both networks (rick_amd/svd.py)
+    svd_train_rest: bool = False                     # with svd_adapt: leave the non-adapted tensors (biases, ...) to the networks' Adam
 
 
 class AdaController:
@@ -498,6 +500,11 @@ class RickTrainer:
             raise ValueError('RickTrainer: cdc_weight > 0 needs the frozen source generator (g_source=)')
         if isinstance(cfg.kml_rank, bool) or not isinstance(cfg.kml_rank, int) or not 0 <= cfg.kml_rank <= 8:
             raise ValueError('RickTrainer: kml_rank must be an integer in 0 ... 8')
+        if cfg.svd_adapt and cfg.kml_rank > 0:
+            raise ValueError('RickTrainer: svd_adapt and kml_rank > 0 are alternatives (both rewrite the frozen weights)')
+        if cfg.svd_adapt and cfg.warmup_iter > 0:
+            raise ValueError('RickTrainer: svd_adapt needs warmup_iter = 0 (the warm-up stage switches D\'s gradients off layer by '
+                             'layer; singular-value adaptation has no such stage)')
         for w in (cfg.dcl_g_weight, cfg.dcl_d_weight):
             if w < 0 or not math.isfinite(w):
                 raise ValueError('RickTrainer: dcl_g_weight and dcl_d_weight must be finite and >= 0')
@@ -559,6 +566,15 @@ class RickTrainer:
             from .kml import KmlState
             self.kml_g = KmlState(self.g_flat, cfg.kml_rank, lr=self.g_optim.lr, betas=self.g_optim.betas)
             self.kml_d = KmlState(self.d_flat, cfg.kml_rank, lr=self.d_optim.lr, betas=self.d_optim.betas)
+        # singular-value adaptation (cfg.svd_adapt): one adapter per network, stepped with the network's lr / betas; the networks'
+        # own optimisers get its freeze mask (RICK's Fisher masks and this mask are alternatives: fisher_sweep refuses)
+        self.svd_g = self.svd_d = None
+        if cfg.svd_adapt:
+            from .svd import SvdAdapter
+            self.svd_g = SvdAdapter(self.g_flat, lr=self.g_optim.lr, betas=self.g_optim.betas)
+            self.svd_d = SvdAdapter(self.d_flat, lr=self.d_optim.lr, betas=self.d_optim.betas)
+            self.g_optim.set_mask(self.svd_g.frozen_mask(rest=cfg.svd_train_rest))
+            self.d_optim.set_mask(self.svd_d.frozen_mask(rest=cfg.svd_train_rest))
         self.ewc = None
         if ewc is not None:
             self.set_ewc(*ewc) if isinstance(ewc, (tuple, list)) else self.set_ewc(ewc)
@@ -592,6 +608,15 @@ class RickTrainer:
     # ---- kernel modulation (rick_amd/kml.py)
     def _kml(self, flat):
         return self.kml_g if flat is self.g_flat else self.kml_d
+
+    def _adapter(self, flat):
+        """The adapter whose grads_ / adam_step / apply_ bracket the network's optimiser step in _run: KML's or FSGAN's (never
+        both), None without one."""
+        if self.cfg.kml_rank > 0:
+            return self._kml(flat)
+        if self.cfg.svd_adapt:
+            return self.svd_g if flat is self.g_flat else self.svd_d
+        return None
 
     def kml_rows_from_masks(self):
         """Flag "frozen and not pruned" on every modulated layer, from the index sets the masks were built from (idx_freeze_*,
@@ -658,6 +683,8 @@ class RickTrainer:
     def enable_graphs(self, on=True):
         if on and self.cfg.kml_rank > 0:
             raise RuntimeError('RickTrainer: hipGraph replay with kernel modulation (kml_rank > 0) is not supported')
+        if on and self.cfg.svd_adapt:
+            raise RuntimeError('RickTrainer: hipGraph replay with singular-value adaptation (svd_adapt) is not supported')
         self.use_graphs = bool(on)
         if self.dp is not None:
             self.dp.hooks_enabled = not self.use_graphs      # a replayed backward runs no Python hooks
@@ -756,9 +783,10 @@ class RickTrainer:
         forward/backward graph and the step returns; the next step replays its head, THEN waits for the exchange, replays the
         pending optimiser graph and continues — the all-reduce of the D gradients travels while the generator forward
         runs (north star: "overlapped with the next micro-batch forward")."""
-        kml = self._kml(flat) if self.cfg.kml_rank > 0 else None
+        kml = self._adapter(flat)
         if kml is not None and key is not None:
-            raise RuntimeError('RickTrainer: a graph=True step with kernel modulation (kml_rank > 0) is not supported')
+            raise RuntimeError('RickTrainer: a graph=True step with ' + ('kernel modulation (kml_rank > 0)' if self.cfg.kml_rank > 0 else
+                               'singular-value adaptation (svd_adapt)') + ' is not supported')
         if pre is not None:
             pre()
         st = None
@@ -778,7 +806,7 @@ class RickTrainer:
                 fb_head()
             fb()
             self._reduce(flat)
-            if kml is not None:                               # the averaged gradient: da / db are identical on every rank
+            if kml is not None:                               # the averaged gradient: da / db (dd) are identical on every rank
                 kml.grads_()
             optim.step()                                      # (the freeze bit leaves the modulated rows alone)
             if kml is not None:
@@ -1222,6 +1250,9 @@ class RickTrainer:
         Returns the two PERSISTENT accumulators (scaled grad^2 per parameter): the next sweep zeroes and refills them in
         place — clone what must outlive it."""
         cfg = self.cfg
+        if cfg.svd_adapt:
+            raise RuntimeError('RickTrainer: fisher_sweep with singular-value adaptation (svd_adapt) is not supported: RICK\'s '
+                               'freeze / prune masks and the adapter\'s mask are alternatives')
         self._finish_pending()
         requires_grad(self.g_ema, True)
         requires_grad(self.d_ema, True)
@@ -1282,6 +1313,8 @@ class RickTrainer:
     # ---- one iteration in the reference's order (:395-589, 697-698)
     def iteration(self, i, real_img, fisher_inputs=None):
         cfg = self.cfg
+        if fisher_inputs is not None and cfg.svd_adapt:
+            raise RuntimeError('RickTrainer: iteration(fisher_inputs=...) with singular-value adaptation (svd_adapt) is not supported')
         if fisher_inputs is not None and i - cfg.warmup_iter >= 0 and (i - cfg.warmup_iter) % cfg.fisher_freq == 0:
             self.fisher_sweep(*fisher_inputs, first=(i == cfg.warmup_iter))
         graph = self.use_graphs and i >= cfg.warmup_iter      # the warm-up stage has its own requires_grad pattern
