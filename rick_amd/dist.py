@@ -5,7 +5,7 @@ The reference's only live parallelism is single-process ``nn.DataParallel`` on D
 feature maps, reduce-add of gradients.  Here every rank owns a full replica and a micro-batch;
 the only data-path exchange is the gradient average before each optimiser step:
 
-  * gradients of one network live in ONE flat buffer (rick_amd.train.FlatParams), cut into
+  * gradients of one network live in ONE flat buffer (rick_amd.flat.FlatParams), cut into
     contiguous buckets (default 32 MiB: large enough that a ring over 7 xGMI links runs at link
     rate, small enough that the first bucket leaves while backward is still producing the rest);
   * a post-accumulate-grad hook per parameter counts down its bucket; when a bucket is complete

@@ -23,13 +23,15 @@ import math
 import torch
 
 from . import _lib
+from .adapter import FlatSlice
+from .flat import FisherAccumulator
 
 
 def _same_device(a, b):
     return a.type == b.type and (a.type != 'cuda' or (a.index or 0) == (b.index or 0))
 
 
-class EwcAnchor:
+class EwcAnchor(FlatSlice):
     """theta* and F of the optimised slice ``[flat.lo:flat.hi]`` of a FlatParams as two fp32 buffers in the slice's own layout:
     the same offsets, zero in the padding between parameters (a padding element adds F (0 - 0)^2 = 0).
 
@@ -40,21 +42,13 @@ class EwcAnchor:
     The anchor also owns the fp64 partial sums and the result of ``penalty_`` (allocated here, once)."""
 
     def __init__(self, flat, source_state, fisher=None):
-        self.flat = flat
-        self.lo, self.hi = flat.lo, flat.hi
-        self.n = self.hi - self.lo
-        self.names = [flat.names[i] for i in flat.opt_idx]
-        self.device = flat.flat.device
+        super().__init__(flat)
+        self.names = self.owned
         self.anchor = self._stage(source_state, 'source_state', False)
         self.fisher = self._stage(fisher, 'fisher', True)
         self.blocks = int(_lib.lib.rick_ewc_blocks(self.n))
         self.partials = torch.zeros(max(1, self.blocks), device=self.device, dtype=torch.float64)
         self.value = torch.zeros((), device=self.device, dtype=torch.float64)
-
-    def segment(self, name):
-        """[start, end) of a parameter inside the two buffers."""
-        lo, hi = self.flat.segment(name)
-        return lo - self.lo, hi - self.lo
 
     def _stage(self, mapping, what, is_fisher):
         """A new buffer in the slice's layout filled from `mapping` — validated completely before anything live is touched."""
@@ -157,7 +151,7 @@ def estimate_fisher(generator, discriminator, latents, fixed_noise=False):
     passes) is restored; RickTrainer.fisher_sweep and its masks are not involved."""
     from torch import autograd
 
-    from .train import FisherAccumulator, g_nonsaturating_loss, g_optim_filter
+    from .train import g_nonsaturating_loss, g_optim_filter
     latents = list(latents)
     if not latents:
         raise ValueError('estimate_fisher: needs at least one latent')

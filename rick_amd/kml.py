@@ -22,35 +22,16 @@ a starts at 0, b ~ N(0, 1): the first W^ is W0 bit for bit and da is non-zero fr
 The flat buffer simply holds the modulated weights: every convolution form, weight pack and gradient kernel works on them
 unchanged.  On the device grads_ and apply_ are the launches of rick_amd/csrc/kml.hip (include/rick_hip.h "KML"): all layers in one
 launch each, 8 B per modulated element, work proportional to the flagged rows, no atomics, bit-identical from run to run.  CPU
-tensors take the same definition composed from torch ops in fp64.  a and b are nn.Parameters re-homed in a FlatParams of their own
-and stepped by a MaskedFlatAdam (the network's lr and betas by default)."""
-import ctypes
-
+tensors take the same definition composed from torch ops in fp64.  Everything an adapter of the slice has in common — names,
+views, the factors' own FlatParams and Adam, the step bracket, the state_dict round trip — is rick_amd/adapter.py's FlatAdapter."""
 import numpy as np
 import torch
 from torch import nn
 
 from . import _lib
+from .adapter import FlatAdapter, flat_f32, upload_table
 
 MAX_RANK = 8
-
-
-class _NoPack:
-    """Stands in for a PackGroup on the factors: MaskedFlatAdam.step reports the parameters it updated to op.bump_weights_epoch,
-    which invalidates EVERY packed weight when one of them belongs to no group — the factors are never packed."""
-    epoch = 0
-
-
-def _view3(p):
-    """(co, ci, taps) of a weight tensor."""
-    shape = tuple(p.shape)
-    if len(shape) == 5:
-        if shape[0] != 1:
-            raise ValueError(f'kml: a 5-D weight needs a leading dim of 1, got {shape}')
-        shape = shape[1:]
-    if len(shape) < 2:
-        raise ValueError(f'kml: a weight needs at least two dims, got {shape}')
-    return shape[0], shape[1], int(np.prod(shape[2:], dtype=np.int64))
 
 
 class KmlTables:
@@ -89,23 +70,15 @@ class KmlTables:
         self.nflags = int(sum(len(x) for x in flags))
         if torch.device(device).type != 'cuda':
             return
-        raw = np.frombuffer(ctypes.string_at(ctypes.addressof(rec), ctypes.sizeof(rec)), dtype=np.uint8).copy()
-        self.layers_dev = torch.from_numpy(raw).to(device)
+        self.layers_dev = upload_table(rec, device)
         self.rows_dev = torch.from_numpy(np.concatenate(rows + [np.zeros(1, np.int32)])).to(device)
         self.blocks_dev = torch.tensor(blocks + [(0, 0)], dtype=torch.int32).reshape(-1).to(device)
         self.flags_dev = torch.from_numpy(np.concatenate(flags)).to(device)
 
 
-def _flat_f32(what, *tensors):
-    dev = tensors[0].device
-    for t in tensors:
-        if not t.is_cuda or t.dtype != torch.float32 or t.dim() != 1 or (t.numel() > 1 and t.stride(0) != 1) or t.device != dev:
-            raise ValueError(f'kml: {what} must be dense 1-D float32 tensors on one HIP device')
-
-
 def apply_tables(w0, w, fac, tables):
     """rick_kml_apply_f32 on raw buffers: W^ into the flagged rows of `w` (the layout of `w0`), from `w0` and the factors."""
-    _flat_f32('w0, w and fac', w0, w, fac)
+    flat_f32('kml', 'w0, w and fac', w0, w, fac)
     if w.numel() != w0.numel():
         raise ValueError('kml: w and w0 must have one length')
     if tables.nblocks == 0:
@@ -121,7 +94,7 @@ def apply_tables(w0, w, fac, tables):
 def grad_tables(grad, w0, fac, dfac, partials, tables):
     """rick_kml_grad_f32 + rick_kml_grad_finish_f32 on raw buffers: da / db of every layer into `dfac` (the layout of `fac`).
     partials: fp32 workspace of at least tables.npart entries."""
-    _flat_f32('grad, w0, fac, dfac and partials', grad, w0, fac, dfac, partials)
+    flat_f32('kml', 'grad, w0, fac, dfac and partials', grad, w0, fac, dfac, partials)
     if grad.numel() != w0.numel() or fac.numel() != dfac.numel() or partials.numel() < tables.npart:
         raise ValueError('kml: grad / w0 and fac / dfac must pair up, partials must hold tables.npart entries')
     from .op.conv import hbm_launch
@@ -137,7 +110,7 @@ def grad_tables(grad, w0, fac, dfac, partials, tables):
                                                      _lib.stream_ptr()), 'rick_kml_grad_finish_f32')
 
 
-class KmlState:
+class KmlState(FlatAdapter):
     """The KML adapter over the optimised slice ``[flat.lo:flat.hi]`` of a FlatParams.
 
     flat: the FlatParams.  rank: R, 1 ... 8, the same for all layers.  names: the modulated parameters (default: every parameter
@@ -149,65 +122,22 @@ class KmlState:
     [co]) and, on the device, the layer table, the compacted row lists and the db partials."""
 
     def __init__(self, flat, rank, names=None, generator=None, lr=0.002, betas=(0.0, 0.99)):
-        from .train import FlatParams, MaskedFlatAdam
         if isinstance(rank, bool) or not isinstance(rank, int) or not 1 <= rank <= MAX_RANK:
             raise ValueError(f'kml: rank must be an integer in 1 ... {MAX_RANK}, got {rank!r}')
-        self.flat, self.rank = flat, rank
-        self.lo, self.hi = flat.lo, flat.hi
-        self.n = self.hi - self.lo
-        self.device = flat.flat.device
-        owned = [flat.names[i] for i in flat.opt_idx]
-        if names is None:
-            names = [n for n in owned if flat.params[flat.index[n]].dim() >= 4]
-        names = list(names)
-        if not names:
-            raise ValueError('kml: no parameter to modulate')
-        if len(set(names)) != len(names):
-            raise ValueError('kml: a name is listed twice')
-        for n in names:
-            if n not in flat.index:
-                raise KeyError(f'kml: the FlatParams has no parameter {n}')
-            if n not in owned:
-                raise ValueError(f'kml: {n} lies outside the optimised slice')
-        self.names = names
-        self.shape3 = {n: _view3(flat.params[flat.index[n]]) for n in names}
+        super().__init__(flat, names, 'kml', lambda p: p.dim() >= 4)
+        self.rank = rank
         if max(ci for _, ci, _ in self.shape3.values()) * rank > 16384:
             raise ValueError('kml: ci * rank must not exceed 16384 (the gradient kernel keeps a layer\'s db in 64 KB of LDS)')
         self.w0 = torch.zeros(self.n, device=self.device, dtype=torch.float32)
-        named = []
-        for n in names:
-            named.append((f'a.{n}', nn.Parameter(torch.zeros(self.shape3[n][0], rank, device=self.device))))
-        for n in names:
+        named = [(f'a.{n}', nn.Parameter(torch.zeros(self.shape3[n][0], rank, device=self.device))) for n in self.names]
+        for n in self.names:
             bn = torch.randn(self.shape3[n][1], rank, generator=generator, dtype=torch.float32)
             named.append((f'b.{n}', nn.Parameter(bn.to(self.device))))
-        self.fac = FlatParams(named)
-        self.a = {n: self.fac.params[self.fac.index[f'a.{n}']] for n in names}
-        self.b = {n: self.fac.params[self.fac.index[f'b.{n}']] for n in names}
-        for p in self.fac.params:
-            p._rick_group = _NoPack
-        self.optim = MaskedFlatAdam(self.fac, lr, tuple(betas))
-        self.rows = {n: torch.zeros(self.shape3[n][0], dtype=torch.bool, device=self.device) for n in names}
+        self._own_factors(named, lr, betas)
+        self.a = {n: self.fac.params[self.fac.index[f'a.{n}']] for n in self.names}
+        self.b = {n: self.fac.params[self.fac.index[f'b.{n}']] for n in self.names}
+        self.rows = {n: torch.zeros(self.shape3[n][0], dtype=torch.bool, device=self.device) for n in self.names}
         self._build_tables()
-
-    # ---- layout
-    def segment(self, name):
-        """[start, end) of a parameter inside ``w0`` (and inside ``flat.flat[lo:hi]`` / ``flat.grad[lo:hi]``)."""
-        lo, hi = self.flat.segment(name)
-        return lo - self.lo, hi - self.lo
-
-    def _w3(self, buf, name):
-        a, b = self.segment(name)
-        return buf[a:b].view(self.shape3[name])
-
-    def weight(self, name):
-        """The live weight as a [co, ci, taps] view of the flat parameter buffer."""
-        return self._w3(self.flat.flat[self.lo:self.hi], name)
-
-    def grad(self, name):
-        return self._w3(self.flat.grad[self.lo:self.hi], name)
-
-    def snapshot(self, name):
-        return self._w3(self.w0, name)
 
     def modulation(self, name):
         """1 + a b^T, [co, ci] (fp32; every row, flagged or not)."""
@@ -219,9 +149,8 @@ class KmlState:
 
     # ---- tables
     def _build_tables(self):
-        specs = [dict(off=self.segment(n)[0], a_off=int(self.fac.offsets[self.fac.index[f'a.{n}']]),
-                      b_off=int(self.fac.offsets[self.fac.index[f'b.{n}']]), shape=self.shape3[n], rows=self.rows[n].cpu().numpy())
-                 for n in self.names]
+        specs = [dict(off=self.segment(n)[0], a_off=self.fac_range(f'a.{n}')[0], b_off=self.fac_range(f'b.{n}')[0],
+                      shape=self.shape3[n], rows=self.rows[n].cpu().numpy()) for n in self.names]
         t = self.tables = KmlTables(specs, self.rank, self.device)
         self.nrows_total, self.nblocks, self.elements = t.nrows_total, t.nblocks, t.elements
         if self.w0.is_cuda and (getattr(self, 'partials', None) is None or self.partials.numel() < max(1, t.npart)):
@@ -249,41 +178,32 @@ class KmlState:
                 enter = f & ~self.rows[n]
                 if bool(enter.any()):
                     self.snapshot(n)[enter] = self.weight(n)[enter]
-                    ai = self.fac.index[f'a.{n}']
-                    lo = int(self.fac.offsets[ai])
-                    hi = lo + self.fac.sizes[ai]
+                    lo, hi, _ = self.fac_range(f'a.{n}')
                     for buf in (self.fac.flat, self.optim.m, self.optim.v):
                         buf[lo:hi].view(-1, self.rank)[enter] = 0
                 self.rows[n] = f.clone()
         self._build_tables()
 
-    # ---- the two passes
-    def grads_(self):
-        """a.grad, b.grad (the adapter's flat gradient buffer) from flat.grad and W0.  No host synchronisation.  With no row
-        flagged only the finishing launch runs (it writes the zeros)."""
-        if not self.w0.is_cuda:
-            return self._grads_cpu()
+    def set_rows_from_index_sets(self, freeze, zero):
+        """set_rows with "frozen and not pruned" on every modulated layer: freeze / zero are {name: filter indices} or None (the
+        index sets RICK's masks are built from); pruned filters are never modulated, a name in neither set flags nothing."""
+        rows = {}
+        for name in self.names:
+            f = np.zeros(self.shape3[name][0], dtype=bool)
+            if freeze is not None and name in freeze:
+                f[np.asarray(freeze[name], dtype=np.int64)] = True
+            if zero is not None and name in zero:
+                f[np.asarray(zero[name], dtype=np.int64)] = False
+            rows[name] = torch.from_numpy(f)
+        self.set_rows(rows)
+
+    # ---- the two passes.  With no row flagged only the finishing launch of grads_ runs (it writes the zeros).
+    def _grads_dev(self):
         grad_tables(self.flat.grad[self.lo:self.hi], self.w0, self.fac.flat, self.fac.grad, self.partials, self.tables)
 
-    def apply_(self):
-        """W^ into the flagged rows of the flat parameter buffer; then the packed weights of the network go stale."""
-        from . import op
-        if not self.w0.is_cuda:
-            self._apply_cpu()
-        else:
-            apply_tables(self.w0, self.flat.flat[self.lo:self.hi], self.fac.flat, self.tables)
-        op.bump_weights_epoch(self.flat.params)
+    def _apply_dev(self):
+        apply_tables(self.w0, self.flat.flat[self.lo:self.hi], self.fac.flat, self.tables)
 
-    def adam_step(self):
-        """One step of the adapter's own Adam on a.grad / b.grad (device tensors only: it is rick_masked_adam_dev_f32)."""
-        self.optim.step()
-
-    def step(self):
-        self.grads_()
-        self.adam_step()
-        self.apply_()
-
-    # ---- the same definition from torch ops in fp64 (CPU tensors)
     def _grads_cpu(self):
         with torch.no_grad():
             self.fac.grad.zero_()
@@ -304,70 +224,27 @@ class KmlState:
                 m = 1.0 + self.a[n].detach().double() @ self.b[n].detach().double().t()
                 self.weight(n)[f] = (self.snapshot(n).double() * m[:, :, None]).to(torch.float32)[f]
 
-    # ---- persistence
-    def state_dict(self):
-        """Copies: 'w0.<name>', 'a.<name>', 'b.<name>' (the parameter's / factors' shapes), 'rows.<name>' (bool [co]), the Adam
-        moments 'm.a.<name>', 'v.a.<name>', 'm.b.<name>', 'v.b.<name>' and 'steps' (int64, one count per factor tensor in the
-        order a.*, b.*)."""
-        out = {}
+    # ---- persistence: 'w0.<name>', 'a.<name>', 'b.<name>' (the parameter's / factors' shapes), 'rows.<name>' (bool [co]), the Adam
+    # moments 'm.a.<name>', 'v.a.<name>', 'm.b.<name>', 'v.b.<name>' and 'steps' (one count per factor tensor in the order a.*, b.*)
+    def _entries(self):
+        out = []
         for n in self.names:
-            p = self.flat.params[self.flat.index[n]]
             a, b = self.segment(n)
-            out[f'w0.{n}'] = self.w0[a:b].clone().view(p.shape)
-            out[f'rows.{n}'] = self.rows[n].clone()
-            for key in ('a', 'b'):
-                i = self.fac.index[f'{key}.{n}']
-                lo = int(self.fac.offsets[i])
-                hi = lo + self.fac.sizes[i]
-                shape = self.fac.params[i].shape
-                out[f'{key}.{n}'] = self.fac.flat[lo:hi].clone().view(shape)
-                out[f'm.{key}.{n}'] = self.optim.m[lo:hi].clone().view(shape)
-                out[f'v.{key}.{n}'] = self.optim.v[lo:hi].clone().view(shape)
-        out['steps'] = torch.tensor(self.optim.steps, dtype=torch.int64)
+            out += [(f'w0.{n}', tuple(self.flat.params[self.flat.index[n]].shape), torch.float32, self.w0[a:b]),
+                    (f'rows.{n}', (self.shape3[n][0],), torch.bool, None)]
+            for key in (f'a.{n}', f'b.{n}'):
+                lo, hi, shape = self.fac_range(key)
+                out += [(key, shape, torch.float32, self.fac.flat[lo:hi]), (f'm.{key}', shape, torch.float32, self.optim.m[lo:hi]),
+                        (f'v.{key}', shape, torch.float32, self.optim.v[lo:hi])]
         return out
 
-    def load_state_dict(self, state):
-        """The inverse of state_dict().  Everything is validated and staged before anything live is touched; then copied IN PLACE
-        (w0, the factors and the moments keep their memory) and the tables are rebuilt.  The flat parameter buffer is not
-        written: call apply_() to re-impose W^."""
-        staged = []
+    def state_dict(self):
+        out = super().state_dict()
+        out.update({f'rows.{n}': self.rows[n].clone() for n in self.names})
+        return out
 
-        def take(key, shape, dtype, dst):
-            if key not in state:
-                raise KeyError(f'kml: the state has no entry {key}')
-            t = state[key]
-            if not torch.is_tensor(t) or tuple(t.shape) != tuple(shape):
-                raise ValueError(f'kml: {key} has shape {tuple(getattr(t, "shape", ()))}, expected {tuple(shape)}')
-            if t.dtype != dtype:
-                raise ValueError(f'kml: {key} has dtype {t.dtype}, expected {dtype}')
-            if dtype != torch.bool and t.is_floating_point() and not bool(torch.isfinite(t).all()):
-                raise ValueError(f'kml: {key} has a non-finite entry')
-            staged.append((dst, t.detach().reshape(-1).to(self.device)))
-
-        rows = {}
+    def _loaded(self, extra):
         for n in self.names:
-            p = self.flat.params[self.flat.index[n]]
-            a, b = self.segment(n)
-            take(f'w0.{n}', p.shape, torch.float32, self.w0[a:b])
-            take(f'rows.{n}', (self.shape3[n][0],), torch.bool, None)
-            rows[n] = staged.pop()[1]
-            for key in ('a', 'b'):
-                i = self.fac.index[f'{key}.{n}']
-                lo = int(self.fac.offsets[i])
-                hi = lo + self.fac.sizes[i]
-                shape = self.fac.params[i].shape
-                take(f'{key}.{n}', shape, torch.float32, self.fac.flat[lo:hi])
-                take(f'm.{key}.{n}', shape, torch.float32, self.optim.m[lo:hi])
-                take(f'v.{key}.{n}', shape, torch.float32, self.optim.v[lo:hi])
-        take('steps', (len(self.optim.steps),), torch.int64, None)
-        steps = [int(s) for s in staged.pop()[1].cpu()]
-        if min(steps) < 0:
-            raise ValueError('kml: steps has a negative entry')
-        with torch.no_grad():
-            for dst, src in staged:
-                dst.copy_(src)
-        for n in self.names:
-            self.rows[n] = rows[n].clone()
-        self.optim.steps[:] = steps
-        self.optim.sync_steps_to_device()
+            self.rows[n] = extra[f'rows.{n}'].clone()
         self._build_tables()
+

@@ -26,8 +26,8 @@ orthogonality (near 1e-7) is part of the model, not an error.
 The flat buffer simply holds W^: every convolution form, weight pack, EMA and checkpoint works on it unchanged.  On the device
 grads_ and apply_ are the launches of rick_amd/csrc/svd.hip (include/rick_hip.h "SVD"): all layers in one launch each on the
 fp32 MFMA, no atomics, bit-identical from run to run and independent of a layer's place in the table.  CPU tensors take the same
-definition composed from torch ops in fp64.  d is an nn.Parameter per layer, re-homed in a FlatParams of its own and stepped by
-a MaskedFlatAdam (the network's lr and betas in the trainer)."""
+definition composed from torch ops in fp64.  Everything an adapter of the slice has in common — names, views, the factors' own
+FlatParams and Adam, the step bracket, the state_dict round trip — is rick_amd/adapter.py's FlatAdapter."""
 import ctypes
 
 import numpy as np
@@ -35,7 +35,7 @@ import torch
 from torch import nn
 
 from . import _lib
-from .kml import _NoPack, _view3
+from .adapter import FlatAdapter, flat_f32, upload_table
 
 
 class SvdTables:
@@ -66,8 +66,7 @@ class SvdTables:
         self.elements = int(sum(int(np.prod(sp['shape'])) for sp in specs))
         if torch.device(device).type != 'cuda':
             return
-        raw = np.frombuffer(ctypes.string_at(ctypes.addressof(rec), ctypes.sizeof(rec)), dtype=np.uint8).copy()
-        self.layers_dev = torch.from_numpy(raw).to(device)
+        self.layers_dev = upload_table(rec, device)
         self.apply_blocks_dev = torch.tensor(ab, dtype=torch.int32).reshape(-1).to(device)
         self.grad_blocks_dev = torch.tensor(gb, dtype=torch.int32).reshape(-1).to(device)
 
@@ -75,16 +74,9 @@ class SvdTables:
         return ctypes.addressof(self.layers_host)
 
 
-def _flat_f32(what, *tensors):
-    dev = tensors[0].device
-    for t in tensors:
-        if not t.is_cuda or t.dtype != torch.float32 or t.dim() != 1 or (t.numel() > 1 and t.stride(0) != 1) or t.device != dev:
-            raise ValueError(f'svd: {what} must be dense 1-D float32 tensors on one HIP device')
-
-
 def apply_tables(w0, w, u, vt, d, tables):
     """rick_svd_apply_f32 on raw buffers: W^ of every layer of the table into `w` (the layout of `w0`)."""
-    _flat_f32('w0, w, u, vt and d', w0, w, u, vt, d)
+    flat_f32('svd', 'w0, w, u, vt and d', w0, w, u, vt, d)
     if w.numel() != w0.numel():
         raise ValueError('svd: w and w0 must have one length')
     if tables.layers_dev.device != w0.device:
@@ -99,7 +91,7 @@ def apply_tables(w0, w, u, vt, d, tables):
 def grad_tables(grad, u, vt, dd, partials, tables):
     """rick_svd_grad_f32 + rick_svd_grad_finish_f32 on raw buffers: dd of every layer into `dd` (the layout of d).  partials: fp32
     workspace of at least tables.npart entries."""
-    _flat_f32('grad, u, vt, dd and partials', grad, u, vt, dd, partials)
+    flat_f32('svd', 'grad, u, vt, dd and partials', grad, u, vt, dd, partials)
     if partials.numel() < tables.npart:
         raise ValueError('svd: partials must hold tables.npart entries')
     if tables.layers_dev.device != grad.device:
@@ -134,7 +126,7 @@ def decompose(w3):
     return U.to(torch.float32).contiguous(), S.to(torch.float32).contiguous(), Vh.to(torch.float32).contiguous()
 
 
-class SvdAdapter:
+class SvdAdapter(FlatAdapter):
     """The FSGAN adapter over the optimised slice ``[flat.lo:flat.hi]`` of a FlatParams.
 
     flat: the FlatParams.  names: the adapted parameters (default: every parameter of the slice with ``dim() >= 2``).  lr / betas:
@@ -146,29 +138,8 @@ class SvdAdapter:
     on the device, the tables and the partials workspace."""
 
     def __init__(self, flat, names=None, lr=0.002, betas=(0.0, 0.99)):
-        from .train import FlatParams, MaskedFlatAdam
-        self.flat = flat
-        self.lo, self.hi = flat.lo, flat.hi
-        self.n = self.hi - self.lo
-        self.device = flat.flat.device
-        owned = [flat.names[i] for i in flat.opt_idx]
-        if names is None:
-            names = [n for n in owned if flat.params[flat.index[n]].dim() >= 2]
-        names = list(names)
-        if not names:
-            raise ValueError('svd: no parameter to adapt')
-        if len(set(names)) != len(names):
-            raise ValueError('svd: a name is listed twice')
-        for n in names:
-            if n not in flat.index:
-                raise KeyError(f'svd: the FlatParams has no parameter {n}')
-            if n not in owned:
-                raise ValueError(f'svd: {n} lies outside the optimised slice')
-        self.names = names
-        try:
-            self.shape3 = {n: _view3(flat.params[flat.index[n]]) for n in names}
-        except ValueError as e:
-            raise ValueError(str(e).replace('kml:', 'svd:')) from None
+        super().__init__(flat, names, 'svd', lambda p: p.dim() >= 2)
+        names = self.names
         self.rank = {n: min(s[0], s[1]) for n, s in self.shape3.items()}
         self.w0 = flat.flat[self.lo:self.hi].detach().clone()
         us, vts, self.s0, self._uoff, self._vtoff = [], [], {}, {}, {}
@@ -185,36 +156,13 @@ class SvdAdapter:
                   for n, s in self.shape3.items()}
         self.vt = {n: self.vt_flat[self._vtoff[n]:self._vtoff[n] + s[2] * self.rank[n] * s[1]].view(s[2], self.rank[n], s[1])
                    for n, s in self.shape3.items()}
-        self.fac = FlatParams([(f'd.{n}', nn.Parameter(torch.zeros(self.shape3[n][2], self.rank[n], device=self.device)))
-                               for n in names])
+        self._own_factors([(f'd.{n}', nn.Parameter(torch.zeros(self.shape3[n][2], self.rank[n], device=self.device)))
+                           for n in names], lr, betas)
         self.d = {n: self.fac.params[self.fac.index[f'd.{n}']] for n in names}
-        for p in self.fac.params:
-            p._rick_group = _NoPack
-        self.optim = MaskedFlatAdam(self.fac, lr, tuple(betas))
-        specs = [dict(off=self.segment(n)[0], u_off=self._uoff[n], vt_off=self._vtoff[n],
-                      d_off=int(self.fac.offsets[self.fac.index[f'd.{n}']]), shape=self.shape3[n]) for n in names]
+        specs = [dict(off=self.segment(n)[0], u_off=self._uoff[n], vt_off=self._vtoff[n], d_off=self.fac_range(f'd.{n}')[0],
+                      shape=self.shape3[n]) for n in names]
         self.tables = SvdTables(specs, self.device)
         self.partials = torch.zeros(self.tables.npart, device=self.device, dtype=torch.float32) if self.w0.is_cuda else None
-
-    # ---- layout
-    def segment(self, name):
-        """[start, end) of a parameter inside ``w0`` (and inside ``flat.flat[lo:hi]`` / ``flat.grad[lo:hi]``)."""
-        lo, hi = self.flat.segment(name)
-        return lo - self.lo, hi - self.lo
-
-    def _w3(self, buf, name):
-        a, b = self.segment(name)
-        return buf[a:b].view(self.shape3[name])
-
-    def weight(self, name):
-        """The live weight as a [co, ci, taps] view of the flat parameter buffer."""
-        return self._w3(self.flat.flat[self.lo:self.hi], name)
-
-    def grad(self, name):
-        return self._w3(self.flat.grad[self.lo:self.hi], name)
-
-    def snapshot(self, name):
-        return self._w3(self.w0, name)
 
     def singular_values(self, name):
         """s0 + d, [taps, r] (fp32): the singular values of the adapted weight along the frozen directions."""
@@ -233,31 +181,12 @@ class SvdAdapter:
         return mask
 
     # ---- the two passes
-    def grads_(self):
-        """d.grad (the adapter's flat gradient buffer) from flat.grad.  No host synchronisation."""
-        if not self.w0.is_cuda:
-            return self._grads_cpu()
+    def _grads_dev(self):
         grad_tables(self.flat.grad[self.lo:self.hi], self.u_flat, self.vt_flat, self.fac.grad, self.partials, self.tables)
 
-    def apply_(self):
-        """W^ into the adapted tensors of the flat parameter buffer; then the packed weights of the network go stale."""
-        from . import op
-        if not self.w0.is_cuda:
-            self._apply_cpu()
-        else:
-            apply_tables(self.w0, self.flat.flat[self.lo:self.hi], self.u_flat, self.vt_flat, self.fac.flat, self.tables)
-        op.bump_weights_epoch(self.flat.params)
+    def _apply_dev(self):
+        apply_tables(self.w0, self.flat.flat[self.lo:self.hi], self.u_flat, self.vt_flat, self.fac.flat, self.tables)
 
-    def adam_step(self):
-        """One step of the adapter's own Adam on d.grad (device tensors only: it is rick_masked_adam_dev_f32)."""
-        self.optim.step()
-
-    def step(self):
-        self.grads_()
-        self.adam_step()
-        self.apply_()
-
-    # ---- the same definition from torch ops in fp64 (CPU tensors)
     def _grads_cpu(self):
         with torch.no_grad():
             for n in self.names:
@@ -268,56 +197,18 @@ class SvdAdapter:
             for n in self.names:
                 self.weight(n).copy_(compose_apply(self.snapshot(n), self.u[n], self.vt[n], self.d[n].detach()).to(torch.float32))
 
-    # ---- persistence
+    # ---- persistence: 'w0.<name>' (the parameter's shape), 'u.<name>' [taps, co, r], 'vt.<name>' [taps, r, ci], 's0.<name>',
+    # 'd.<name>' and the Adam moments 'm.d.<name>', 'v.d.<name>' [taps, r], and 'steps' (one count per d)
     def _entries(self):
-        """(key, shape, live destination) of every tensor of the state, in a fixed order."""
         out = []
         for n in self.names:
-            p = self.flat.params[self.flat.index[n]]
             a, b = self.segment(n)
-            i = self.fac.index[f'd.{n}']
-            lo = int(self.fac.offsets[i])
-            hi = lo + self.fac.sizes[i]
-            shape = tuple(self.d[n].shape)
-            out += [(f'w0.{n}', tuple(p.shape), self.w0[a:b]), (f'u.{n}', tuple(self.u[n].shape), self.u[n]),
-                    (f'vt.{n}', tuple(self.vt[n].shape), self.vt[n]), (f's0.{n}', shape, self.s0[n]),
-                    (f'd.{n}', shape, self.fac.flat[lo:hi]), (f'm.d.{n}', shape, self.optim.m[lo:hi]),
-                    (f'v.d.{n}', shape, self.optim.v[lo:hi])]
+            lo, hi, shape = self.fac_range(f'd.{n}')
+            tensors = [(f'w0.{n}', tuple(self.flat.params[self.flat.index[n]].shape), self.w0[a:b]),
+                       (f'u.{n}', tuple(self.u[n].shape), self.u[n]), (f'vt.{n}', tuple(self.vt[n].shape), self.vt[n]),
+                       (f's0.{n}', shape, self.s0[n]), (f'd.{n}', shape, self.fac.flat[lo:hi]),
+                       (f'm.d.{n}', shape, self.optim.m[lo:hi]), (f'v.d.{n}', shape, self.optim.v[lo:hi])]
+            out += [(key, sh, torch.float32, dst) for key, sh, dst in tensors]
         return out
 
-    def state_dict(self):
-        """Copies: 'w0.<name>' (the parameter's shape), 'u.<name>' [taps, co, r], 'vt.<name>' [taps, r, ci], 's0.<name>',
-        'd.<name>' and the Adam moments 'm.d.<name>', 'v.d.<name>' [taps, r], and 'steps' (int64, one count per d)."""
-        out = {key: dst.detach().clone().view(shape) for key, shape, dst in self._entries()}
-        out['steps'] = torch.tensor(self.optim.steps, dtype=torch.int64)
-        return out
 
-    def load_state_dict(self, state):
-        """The inverse of state_dict().  Everything is validated and staged before anything live is touched; then copied IN PLACE
-        (w0, the factors, d and the moments keep their memory).  The flat parameter buffer is not written: call apply_() to
-        re-impose W^."""
-        staged = []
-        for key, shape, dst in self._entries():
-            if key not in state:
-                raise KeyError(f'svd: the state has no entry {key}')
-            t = state[key]
-            if not torch.is_tensor(t) or tuple(t.shape) != shape:
-                raise ValueError(f'svd: {key} has shape {tuple(getattr(t, "shape", ()))}, expected {shape}')
-            if t.dtype != torch.float32:
-                raise ValueError(f'svd: {key} has dtype {t.dtype}, expected {torch.float32}')
-            if not bool(torch.isfinite(t).all()):
-                raise ValueError(f'svd: {key} has a non-finite entry')
-            staged.append((dst, t.detach().to(self.device)))
-        if 'steps' not in state:
-            raise KeyError('svd: the state has no entry steps')
-        s = state['steps']
-        if not torch.is_tensor(s) or s.dtype != torch.int64 or tuple(s.shape) != (len(self.optim.steps),):
-            raise ValueError(f'svd: steps must be an int64 tensor of shape ({len(self.optim.steps)},)')
-        steps = [int(x) for x in s.cpu()]
-        if min(steps) < 0:
-            raise ValueError('svd: steps has a negative entry')
-        with torch.no_grad():
-            for dst, src in staged:
-                dst.copy_(src.reshape(dst.shape))
-        self.optim.steps[:] = steps
-        self.optim.sync_steps_to_device()

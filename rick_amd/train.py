@@ -1,6 +1,6 @@
 """Host side of the RICK adaptation loop on the MI355X engine: losses and gradient penalties,
 the Fisher-information sweep with on-device grad^2 accumulation and per-filter reduction, the
-freeze / fine-tune / prune decisions and masks, the masked flat Adam + EMA, and the per-iteration
+freeze / fine-tune / prune decisions and masks (flat masked Adam + EMA: rick_amd/flat.py), and the per-iteration
 control flow of ``train()`` (train_dynamic_update_prune.py:159-699).
 
 Work the reference performs and then discards is skipped (SURVEY.md §8a footnote): the D step
@@ -23,6 +23,7 @@ from . import augment as A
 from . import diffaug as DA
 from .augment import augment_fused
 from .diffaug import diffaug_fused
+from .flat import FLAT_ALIGN, FisherAccumulator, FlatParams, MaskedFlatAdam, ema_flat  # noqa: F401  (re-exported)
 from .param_block import StepParamBlock
 
 
@@ -77,161 +78,7 @@ def requires_grad(model, flag=True, only=None):
             p.requires_grad = flag
 
 
-# ------------------------------------------------------------------ flat params / Adam / EMA
-FLAT_ALIGN = 64      # floats
-
-
-class FlatParams:
-    """Re-homes the parameters of a network into ONE flat fp32 buffer (each parameter becomes a view)
-    with a matching flat gradient buffer (``p.grad`` are views too).  `opt_filter` marks the parameters an
-    optimiser owns; they must be contiguous in registration order (true for both reference networks:
-    ``convs.*`` of G, ``convs.1-6 + final_*`` of D) so that one kernel covers mask + Adam of the whole
-    slice, one memset zeroes its gradients, RCCL reduces contiguous buckets, and one kernel does the EMA
-    of the entire network."""
-
-    def __init__(self, named_params, opt_filter=None):
-        named_params = list(named_params)
-        self.names = [n for n, _ in named_params]
-        self.params = [p for _, p in named_params]
-        sizes = [p.numel() for p in self.params]
-        # every parameter starts on a 256-byte boundary (a bias that follows the 1-element noise strength would
-        # otherwise be misaligned for the float4 kernels); offsets[i + 1] is the START of parameter i + 1, the
-        # padding in between stays zero (zero gradient: Adam, EMA and the all-reduce leave it zero)
-        self.sizes = sizes
-        starts, pos = [], 0
-        for n in sizes:
-            starts.append(pos)
-            pos += (n + FLAT_ALIGN - 1) // FLAT_ALIGN * FLAT_ALIGN
-        self.offsets = np.array(starts + [pos], dtype=np.int64)
-        self.total = int(self.offsets[-1])
-        dev = self.params[0].device
-        self.flat = torch.zeros(self.total, device=dev, dtype=torch.float32)
-        self.grad = torch.zeros(self.total, device=dev, dtype=torch.float32)
-        for p, o, n in zip(self.params, self.offsets, sizes):
-            self.flat[o:o + n].copy_(p.data.reshape(-1))
-            p.data = self.flat[o:o + n].view(p.shape)
-            p.grad = self.grad[o:o + n].view(p.shape)
-        self.index = {n: i for i, n in enumerate(self.names)}
-        self.opt_idx = [i for i, n in enumerate(self.names) if opt_filter is None or opt_filter(n)]
-        if self.opt_idx and self.opt_idx != list(range(self.opt_idx[0], self.opt_idx[-1] + 1)):
-            raise RuntimeError('FlatParams: optimised parameters must be contiguous in registration order')
-        self.lo = int(self.offsets[self.opt_idx[0]]) if self.opt_idx else 0
-        self.hi = int(self.offsets[self.opt_idx[-1] + 1]) if self.opt_idx else 0
-
-    def zero_grad(self):
-        self.grad[self.lo:self.hi].zero_()
-
-    def segment(self, name):
-        i = self.index[name]
-        return int(self.offsets[i]), int(self.offsets[i]) + self.sizes[i]
-
-
-class MaskedFlatAdam:
-    """torch.optim.Adam(lr, betas, eps=1e-8) over the optimised slice of a FlatParams, with RICK's
-    freeze / prune masks applied in the same kernel (train_dynamic_update_prune.py:427-438, 522-540).
-    Parameters whose ``requires_grad`` is False at step time are skipped exactly like torch skips
-    ``grad is None`` (per-parameter step counts, used by the warm-up stage :202-211)."""
-
-    def __init__(self, flat, lr, betas, eps=1e-8):
-        self.fp, self.lr, self.betas, self.eps = flat, lr, betas, eps
-        self.m = torch.zeros_like(flat.flat)
-        self.v = torch.zeros_like(flat.flat)
-        self.steps = [0] * len(flat.params)          # host mirror of steps_dev (checkpoints, run grouping)
-        # step counters and bias corrections also live on the device (rick_adam_prepare_f32), so an optimiser step
-        # depends on device state only and a captured hipGraph of a whole train step can be replayed
-        self.steps_dev = torch.zeros(len(flat.params), device=flat.flat.device, dtype=torch.int32)
-        self.bc = torch.ones(8, 2, device=flat.flat.device, dtype=torch.float32)      # one row per run of equal step count
-        self.mask = None            # uint8 flat: bit0 freeze, bit1 prune
-        self.before_step = None     # callable run at the top of step(): a term added to flat.grad after the gradient exchange
-        self.last_runs = []         # [(first param, last param)] of the most recent step()
-
-    def set_mask(self, mask):
-        if self.mask is not None and self.mask.shape == mask.shape:
-            self.mask.copy_(mask)   # in place: launches captured in a graph keep reading the same buffer
-        else:
-            self.mask = mask
-
-    def sync_steps_to_device(self):
-        self.steps_dev.copy_(torch.tensor(self.steps, dtype=torch.int32))
-
-    def note_replayed_step(self):
-        """A captured step() was replayed: the device counters advanced, mirror it on the host."""
-        for i0, i1 in self.last_runs:
-            for i in range(i0, i1 + 1):
-                self.steps[i] += 1
-
-    def step(self):
-        if self.before_step is not None:
-            self.before_step()
-        fp = self.fp
-        idx = fp.opt_idx
-        active = {i: fp.params[i].requires_grad for i in idx}
-        k, n = 0, len(idx)
-        runs = []
-        while k < n:
-            i = idx[k]
-            if not active[i]:
-                k += 1
-                continue
-            kk = k
-            self.steps[i] += 1
-            while kk + 1 < n and active[idx[kk + 1]] and self.steps[idx[kk + 1]] + 1 == self.steps[i]:
-                kk += 1
-                self.steps[idx[kk]] += 1
-            lo, hi = int(fp.offsets[i]), int(fp.offsets[idx[kk] + 1])
-            b1, b2 = self.betas
-            mk = None if self.mask is None else self.mask[lo:hi]
-            if len(runs) >= self.bc.shape[0]:
-                raise RuntimeError('MaskedFlatAdam: too many runs of distinct step counts')
-            bc = self.bc[len(runs)]
-            check(lib.rick_adam_prepare_f32(ptr(self.steps_dev), i, idx[kk] - i + 1, b1, b2, ptr(bc), stream_ptr()),
-                  'rick_adam_prepare_f32')
-            from .op.conv import hbm_launch
-            check(hbm_launch('masked_adam', (28 + (1 if mk is not None else 0)) * (hi - lo), lib.rick_masked_adam_dev_f32,
-                             ptr(fp.flat[lo:hi]), ptr(fp.grad[lo:hi]), ptr(self.m[lo:hi]), ptr(self.v[lo:hi]), ptr(mk), hi - lo,
-                             self.lr, b1, b2, self.eps, ptr(bc), stream_ptr()), 'rick_masked_adam_dev_f32')
-            runs.append((i, idx[kk]))
-            k = kk + 1
-        self.last_runs = runs
-        op.bump_weights_epoch(fp.params)
-
-
-def ema_flat(ema_flat_params, flat_params, decay):
-    """accumulate() of the reference (train_dynamic_update_prune.py:68-73) over every parameter of a
-    network in ONE launch (both sides are FlatParams with the same layout)."""
-    if ema_flat_params.total != flat_params.total:
-        raise RuntimeError('ema_flat: layouts differ')
-    check(lib.rick_ema_f32(ptr(ema_flat_params.flat), ptr(flat_params.flat), flat_params.total, decay, stream_ptr()),
-          'rick_ema_f32')
-    op.bump_weights_epoch(ema_flat_params.params)
-
-
 # ------------------------------------------------------------------------ Fisher sweep
-class FisherAccumulator:
-    """Device-side replacement for the per-sample ``.cpu().numpy()`` accumulation of grad^2
-    (train_dynamic_update_prune.py:252-263): acc += g^2 in one fused kernel per tensor."""
-
-    def __init__(self, named_params):
-        self.names = [n for n, _ in named_params]
-        self.acc = {n: torch.zeros_like(p, memory_format=torch.contiguous_format) for n, p in named_params}
-
-    def add(self, grads):
-        for n, g in zip(self.names, grads):
-            if g is None:
-                continue
-            g = g.contiguous()
-            check(lib.rick_sq_accumulate_f32(ptr(self.acc[n]), ptr(g), g.numel(), stream_ptr()),
-                  'rick_sq_accumulate_f32')
-
-    def scale_(self, s):
-        for v in self.acc.values():
-            v.mul_(s)
-
-    def zero_(self):
-        for v in self.acc.values():
-            v.zero_()
-
-
 def filter_mean(t, filter_dim):
     """Mean over every dim except `filter_dim` with one wavefront per filter
     (rick_filter_reduce_f32).  Supports filter_dim 0 ([F, ...]) and 1 of a [1, F, ...] tensor."""
@@ -560,21 +407,24 @@ class RickTrainer:
         self._ada_sum = torch.zeros((), device=self.device) if cfg.augment and self.ada.adaptive else None
         if dp is not None:
             dp.attach(self.g_flat, self.d_flat)
-        # kernel modulation of the frozen filters (cfg.kml_rank > 0): one adapter per network, stepped with the network's lr / betas
-        self.kml_g = self.kml_d = None
+        # the slice adapters (rick_amd/adapter.py): kernel modulation of the frozen filters (cfg.kml_rank > 0) or singular-value
+        # adaptation (cfg.svd_adapt), one per network, stepped with the network's lr / betas.  With svd_adapt the networks' own
+        # optimisers get its freeze mask (RICK's Fisher masks and this mask are alternatives: fisher_sweep refuses)
+        nets = ((self.g_flat, self.g_optim), (self.d_flat, self.d_optim))
+        self._adapters, self._adapted_by = {}, None         # FlatParams -> its adapter; what the messages call the feature
+        self.kml_g = self.kml_d = self.svd_g = self.svd_d = None
         if cfg.kml_rank > 0:
-            from .kml import KmlState
-            self.kml_g = KmlState(self.g_flat, cfg.kml_rank, lr=self.g_optim.lr, betas=self.g_optim.betas)
-            self.kml_d = KmlState(self.d_flat, cfg.kml_rank, lr=self.d_optim.lr, betas=self.d_optim.betas)
-        # singular-value adaptation (cfg.svd_adapt): one adapter per network, stepped with the network's lr / betas; the networks'
-        # own optimisers get its freeze mask (RICK's Fisher masks and this mask are alternatives: fisher_sweep refuses)
-        self.svd_g = self.svd_d = None
+            from . import kml
+            self._adapted_by = 'kernel modulation (kml_rank > 0)'
+            self._adapters = {flat: kml.KmlState(flat, cfg.kml_rank, lr=optim.lr, betas=optim.betas) for flat, optim in nets}
+            self.kml_g, self.kml_d = self._adapters.values()
         if cfg.svd_adapt:
-            from .svd import SvdAdapter
-            self.svd_g = SvdAdapter(self.g_flat, lr=self.g_optim.lr, betas=self.g_optim.betas)
-            self.svd_d = SvdAdapter(self.d_flat, lr=self.d_optim.lr, betas=self.d_optim.betas)
-            self.g_optim.set_mask(self.svd_g.frozen_mask(rest=cfg.svd_train_rest))
-            self.d_optim.set_mask(self.svd_d.frozen_mask(rest=cfg.svd_train_rest))
+            from . import svd
+            self._adapted_by = 'singular-value adaptation (svd_adapt)'
+            self._adapters = {flat: svd.SvdAdapter(flat, lr=optim.lr, betas=optim.betas) for flat, optim in nets}
+            self.svd_g, self.svd_d = self._adapters.values()
+            for flat, optim in nets:
+                optim.set_mask(self._adapters[flat].frozen_mask(rest=cfg.svd_train_rest))
         self.ewc = None
         if ewc is not None:
             self.set_ewc(*ewc) if isinstance(ewc, (tuple, list)) else self.set_ewc(ewc)
@@ -605,34 +455,21 @@ class RickTrainer:
         value = penalty_(a, self.cfg.ewc_weight, None if mask is None else mask[a.lo:a.hi])
         self.losses['ewc'] = value.detach()     # a new alias of the anchor's result tensor: registered as an output of a capture
 
-    # ---- kernel modulation (rick_amd/kml.py)
-    def _kml(self, flat):
-        return self.kml_g if flat is self.g_flat else self.kml_d
-
+    # ---- the slice adapters (rick_amd/adapter.py)
     def _adapter(self, flat):
         """The adapter whose grads_ / adam_step / apply_ bracket the network's optimiser step in _run: KML's or FSGAN's (never
         both), None without one."""
-        if self.cfg.kml_rank > 0:
-            return self._kml(flat)
-        if self.cfg.svd_adapt:
-            return self.svd_g if flat is self.g_flat else self.svd_d
-        return None
+        return self._adapters.get(flat)
+
+    def _no_graphs(self, how):
+        raise RuntimeError(f'RickTrainer: {how} with {self._adapted_by} is not supported')
 
     def kml_rows_from_masks(self):
         """Flag "frozen and not pruned" on every modulated layer, from the index sets the masks were built from (idx_freeze_*,
-        zero_idx_*): pruned filters are never modulated.  Called when a Fisher sweep installs new masks; a no-op without KML."""
+        zero_idx_*).  Called when a Fisher sweep installs new masks; a no-op without KML."""
         for kml, freeze, zero in ((self.kml_g, self.idx_freeze_g, self.zero_idx_g), (self.kml_d, self.idx_freeze_d, self.zero_idx_d)):
-            if kml is None:
-                continue
-            rows = {}
-            for name in kml.names:
-                f = np.zeros(kml.shape3[name][0], dtype=bool)
-                if freeze is not None and name in freeze:
-                    f[np.asarray(freeze[name], dtype=np.int64)] = True
-                if zero is not None and name in zero:
-                    f[np.asarray(zero[name], dtype=np.int64)] = False
-                rows[name] = torch.from_numpy(f)
-            kml.set_rows(rows)
+            if kml is not None:
+                kml.set_rows_from_index_sets(freeze, zero)
 
     # ---- gradient flags of the discriminator for the current stage (:202-211)
     def _set_d_stage(self, i):
@@ -681,10 +518,8 @@ class RickTrainer:
     # (style-mixing index) is written into device scalars before the replay.  With data parallelism the capture is
     # split around the gradient all-reduce (forward/backward graph -> RCCL -> optimiser graph).
     def enable_graphs(self, on=True):
-        if on and self.cfg.kml_rank > 0:
-            raise RuntimeError('RickTrainer: hipGraph replay with kernel modulation (kml_rank > 0) is not supported')
-        if on and self.cfg.svd_adapt:
-            raise RuntimeError('RickTrainer: hipGraph replay with singular-value adaptation (svd_adapt) is not supported')
+        if on and self._adapters:
+            self._no_graphs('hipGraph replay')
         self.use_graphs = bool(on)
         if self.dp is not None:
             self.dp.hooks_enabled = not self.use_graphs      # a replayed backward runs no Python hooks
@@ -783,10 +618,9 @@ class RickTrainer:
         forward/backward graph and the step returns; the next step replays its head, THEN waits for the exchange, replays the
         pending optimiser graph and continues — the all-reduce of the D gradients travels while the generator forward
         runs (north star: "overlapped with the next micro-batch forward")."""
-        kml = self._adapter(flat)
-        if kml is not None and key is not None:
-            raise RuntimeError('RickTrainer: a graph=True step with ' + ('kernel modulation (kml_rank > 0)' if self.cfg.kml_rank > 0 else
-                               'singular-value adaptation (svd_adapt)') + ' is not supported')
+        adapter = self._adapter(flat)
+        if adapter is not None and key is not None:
+            self._no_graphs('a graph=True step')
         if pre is not None:
             pre()
         st = None
@@ -806,12 +640,12 @@ class RickTrainer:
                 fb_head()
             fb()
             self._reduce(flat)
-            if kml is not None:                               # the averaged gradient: da / db (dd) are identical on every rank
-                kml.grads_()
-            optim.step()                                      # (the freeze bit leaves the modulated rows alone)
-            if kml is not None:
-                kml.adam_step()
-                kml.apply_()
+            if adapter is not None:                           # the averaged gradient: da / db (dd) are identical on every rank
+                adapter.grads_()
+            optim.step()                                      # (the freeze bit leaves the adapted weights alone)
+            if adapter is not None:
+                adapter.adam_step()
+                adapter.apply_()
             return
         split = self.dp is not None and getattr(self.dp, 'active', True)
         if 'graphs' not in st:

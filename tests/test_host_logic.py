@@ -119,6 +119,14 @@ def test_decisions_equal_reference_block(golden, qtag, fq, pq):
     assert sum(len(v) for v in zero_g.values()) >= sum(len(v) for v in pr_g.values())
 
 
+def test_train_re_exports_the_flat_buffers():
+    """rick_amd.flat is their home; `from rick_amd.train import FlatParams` keeps meaning the same object."""
+    from rick_amd import flat, train
+    for name in ('FlatParams', 'MaskedFlatAdam', 'FisherAccumulator', 'ema_flat', 'FLAT_ALIGN'):
+        assert getattr(train, name) is getattr(flat, name), name
+    assert FlatParams is flat.FlatParams and flat.FLAT_ALIGN == 64
+
+
 def test_flat_params_and_masks_cpu():
     from rick_amd.models import Generator
     g = Generator(16, 512, 8)

@@ -239,6 +239,61 @@ def test_trainer_config_checks():
     assert TrainConfig().kml_rank == 0
 
 
+# ---- trainer: construction and step order with a stand-in (what the trainer uses of an adapter, and nothing else) ---------------
+class _StandInKml:
+    built = []
+
+    def __init__(self, flat, rank, names=None, generator=None, lr=None, betas=None):
+        self.flat, self.rank, self.lr, self.betas, self.log = flat, rank, lr, betas, None
+        _StandInKml.built.append(self)
+
+    def grads_(self):
+        self.log.append('grads_')
+
+    def adam_step(self):
+        self.log.append('adam_step')
+
+    def apply_(self):
+        self.log.append('apply_')
+
+
+def _make(monkeypatch, **cfg):
+    from rick_amd import kml
+    from rick_amd.models import Discriminator, Generator
+    from rick_amd.train import RickTrainer, TrainConfig
+    monkeypatch.setattr(kml, 'KmlState', _StandInKml)
+    del _StandInKml.built[:]
+    torch.manual_seed(0)
+    nets = [f(32, *a, channel_multiplier=1) for f, a in ((Generator, (512, 2)), (Discriminator, ())) * 2]
+    return RickTrainer(TrainConfig(size=32, batch=2, n_mlp=2, warmup_iter=0, **cfg), *nets)
+
+
+def test_step_order(monkeypatch):
+    tr = _make(monkeypatch, kml_rank=2)
+    assert [k.flat for k in _StandInKml.built] == [tr.g_flat, tr.d_flat] and (tr.kml_g, tr.kml_d) == tuple(_StandInKml.built)
+    assert (tr.kml_g.rank, tr.kml_g.lr, tr.kml_g.betas) == (2, tr.g_optim.lr, tr.g_optim.betas)
+    assert (tr.kml_d.rank, tr.kml_d.lr, tr.kml_d.betas) == (2, tr.d_optim.lr, tr.d_optim.betas)
+    assert tr.svd_g is None and tr.svd_d is None and tr.g_optim.mask is None
+    with pytest.raises(RuntimeError, match='hipGraph replay with kernel modulation'):
+        tr.enable_graphs(True)
+    with pytest.raises(RuntimeError, match='graph=True step with kernel modulation'):
+        tr._run('g', lambda: None, tr.g_flat, tr.g_optim)
+    for flat, optim, mine, other in ((tr.g_flat, tr.g_optim, tr.kml_g, tr.kml_d), (tr.d_flat, tr.d_optim, tr.kml_d, tr.kml_g)):
+        log, stray = [], []
+        mine.log, other.log = log, stray
+        monkeypatch.setattr(tr, '_reduce', lambda f, log=log: log.append(('reduce', f)))
+        monkeypatch.setattr(optim, 'step', lambda log=log: log.append('optim.step'))
+        tr._run(None, lambda log=log: log.append('fb'), flat, optim, pre=lambda log=log: log.append('pre'))
+        assert log == ['pre', 'fb', ('reduce', flat), 'grads_', 'optim.step', 'adam_step', 'apply_'] and not stray
+    # off: the step is the plain one
+    tr = _make(monkeypatch)
+    assert tr.kml_g is None and tr.kml_d is None and not _StandInKml.built
+    log = []
+    monkeypatch.setattr(tr.g_optim, 'step', lambda: log.append('optim.step'))
+    tr._run(None, lambda: log.append('fb'), tr.g_flat, tr.g_optim)
+    assert log == ['fb', 'optim.step']
+
+
 def test_c_entries_reject_bad_arguments():
     """RICK_EINVAL (22) from every entry, before any launch: no GPU involved."""
     import ctypes
