@@ -48,33 +48,22 @@ RICK_WGRAD_NOPIPE / RICK_WR_TILE switches exist in the experiment build only.
 import ctypes
 import math
 import types
-import zlib
 
 import pytest
 import torch
 
 from rick_amd.synth import synth_tensor
+from tests.forms_common import (SENT, Fenced, Guarded, cdiv, f32, fenced, fine, ilog2_ceil, ints, p, sat_count, scales,
+                                split_image, stream)
 
 gpu = pytest.mark.gpu
-DEV = 'cuda'
-PAD = 64                      # floats of guard band either side (a multiple of 4: the 16-byte alignment is kept)
-SENT = -7777.125              # no exact-mode result can equal it (asserted)
 EINVAL = 22
 LDS_MAX = 160 * 1024
 K_ROUND = 6                   # extra roundings on a term (module docstring)
-AMAX_FLOATS, AMAX_STRIDE = 512, 32        # a running-maximum word: 16 slots, one per 128-byte line (include/rick_hip.h)
 
 
 def case(**kw):
     return types.SimpleNamespace(**kw)
-
-
-def f32(v):
-    return float(torch.tensor(v, dtype=torch.float32))
-
-
-def cdiv(a, b):
-    return -(-a // b)
 
 
 # ---------------------------------------------------------------------------------------------------------- geometries
@@ -112,13 +101,6 @@ def make_geom(c, alpha=0.25):
 
 
 # ------------------------------------------------------------------------------------------ host-side launcher replay
-def ilog2_ceil(v):
-    l = 0
-    while (1 << l) < v:
-        l += 1
-    return l
-
-
 def make_tiling(g, tile=64):
     """conv_tiling.h make_tiling(g, 64, ..): the fields the weight gradient uses."""
     tl = ilog2_ceil(tile)
@@ -378,36 +360,6 @@ DEVICE = [(c, m) for c in CASES for m in modes_of(c)]
 
 
 # ----------------------------------------------------------------------------------------------------------- inputs
-def _gen(key):
-    gen = torch.Generator(device='cpu')
-    gen.manual_seed(zlib.crc32(key.encode()) & 0x7FFFFFFF)
-    return gen
-
-
-def ints(key, shape, amp):
-    """Non-zero integers in [-amp, amp] as fp32, both signs."""
-    gen = _gen(key)
-    mag = torch.randint(1, amp + 1, tuple(shape), generator=gen).float()
-    return mag * (torch.randint(0, 2, tuple(shape), generator=gen).float() * 2 - 1)
-
-
-def fine(key, shape):
-    """sign * (k + m * 2**-10), k in {2, 3}, m in {1, 3}: |v| in (2, 4) with the 12th significant bit set — fp16 cannot hold it."""
-    gen = _gen(key)
-    k = torch.randint(2, 4, tuple(shape), generator=gen).float()
-    m = torch.randint(0, 2, tuple(shape), generator=gen).float() * 2 + 1
-    v = (k + m * 2.0 ** -10) * (torch.randint(0, 2, tuple(shape), generator=gen).float() * 2 - 1)
-    assert bool((v.half().float() != v).all())
-    return v
-
-
-def scales(key, shape, mode):
-    gen = _gen(key)
-    if mode == 'bound':
-        return 0.5 + torch.rand(tuple(shape), generator=gen)
-    return torch.pow(2.0, torch.randint(-1, 2, tuple(shape), generator=gen).float())
-
-
 def shifted(c, B, dy, dx):
     """B [N, IH, IW, Ci] -> [N, GH, GW, Ci]: B[n, py*is + dy, px*is + dx], zero outside the input."""
     is_ = KINDS[c.kind][0]
@@ -624,72 +576,6 @@ def test_exact_inputs_fit_and_the_bound_is_not_tighter_than_the_split():
 
 
 # ----------------------------------------------------------------------------------------------------- device helpers
-class Guarded:
-    """numel floats between two sentinel bands."""
-
-    def __init__(self, numel, src=None):
-        self.buf = torch.full((PAD + numel + PAD,), SENT, device=DEV, dtype=torch.float32)
-        self.lo, self.hi = PAD, PAD + numel
-        self.v = self.buf[self.lo:self.hi]
-        assert self.v.data_ptr() % 16 == 0
-        if src is not None:
-            self.v.copy_(src.reshape(-1))
-
-    def assert_bands(self, what):
-        assert bool((self.buf[:self.lo] == SENT).all()) and bool((self.buf[self.hi:] == SENT).all()), f'{what}: wrote outside its buffer'
-
-    def untouched(self):
-        return bool((self.buf == SENT).all())
-
-
-class Fenced:
-    """An operand as a view into a larger buffer with NaN on both sides (`off` floats of extra offset misalign it): a read
-    outside the operand but inside the allocation poisons the result.  image = True: the fence is NaN as fp16 halves."""
-
-    def __init__(self, numel, src=None, off=0, image=False):
-        n4 = cdiv(numel, 4) * 4
-        if image:
-            self.buf = torch.full((PAD + off + n4 + PAD,), 0x7E007E00, device=DEV, dtype=torch.int32).view(torch.float32)
-        else:
-            self.buf = torch.full((PAD + off + n4 + PAD,), float('nan'), device=DEV, dtype=torch.float32)
-        self.v = self.buf[PAD + off:PAD + off + numel]
-        assert self.v.data_ptr() % 16 == 4 * (off % 4)
-        if src is not None:
-            self.v.copy_(src.reshape(-1))
-
-
-def p(gd):
-    return None if gd is None else gd.v.data_ptr()
-
-
-def fenced(tn, off=0):
-    return None if tn is None else Fenced(tn.numel(), tn, off)
-
-
-def stream():
-    from rick_amd._lib import stream_ptr
-    return stream_ptr()
-
-
-def sat_count():
-    from rick_amd._lib import check, lib
-    cnt = ctypes.c_uint(0)
-    check(lib.rick_saturation_count(ctypes.byref(cnt), 0), 'rick_saturation_count')
-    return cnt.value
-
-
-def split_image(tn):
-    """rick_split_pack_f32 of an fp32 tensor under its exact maximum -> (image, header), both fenced."""
-    from rick_amd._lib import lib
-    word = torch.zeros(AMAX_FLOATS)
-    word[3 * AMAX_STRIDE] = float(tn.abs().max())
-    src, wd = fenced(tn), fenced(word)
-    img, hdr = Fenced(tn.numel(), image=True), Fenced(4)
-    assert lib.rick_split_pack_f32(p(src), p(img), p(hdr), p(wd), None, 1.0, tn.numel() // tn.shape[-1], tn.shape[-1], stream()) == 0
-    torch.cuda.synchronize()
-    return img, hdr
-
-
 def launch(c, b, ops, gw, ws):
     from rick_amd._lib import lib
     s_co, s_ci, s_t = b.strides
