@@ -1,7 +1,8 @@
-"""What the kernel-forms tests share (test_gpu_wgrad_forms.py, test_gpu_igemm_forms.py): guarded and fenced device buffers, the
-integer / 12-bit / scale generators of the exact modes, split images, the saturation counter.  A plain module: no fixtures, no
-pytest hooks."""
+"""What the kernel-forms tests share (test_gpu_wgrad_forms.py, test_gpu_igemm_forms.py, test_gpu_convt2_forms.py): guarded and
+fenced device buffers, the integer / 12-bit / scale generators of the exact modes, split images, the saturation counter, the
+NaN-fence and amax-word checks, the terms of the a-priori bound.  A plain module: no fixtures, no pytest hooks."""
 import ctypes
+import math
 import zlib
 
 import torch
@@ -111,6 +112,46 @@ def sat_count():
     cnt = ctypes.c_uint(0)
     check(lib.rick_saturation_count(ctypes.byref(cnt), 0), 'rick_saturation_count')
     return cnt.value
+
+
+def nan_fence_ok(fd):
+    """The bands of a Fenced buffer still hold what they were filled with (a view the device writes: the packed weight)."""
+    n = fd.buf.numel() - fd.v.numel()
+    lo = fd.v.data_ptr() - fd.buf.data_ptr() >> 2
+    bits = fd.buf.view(torch.int32)
+    want = bits[0].item()
+    return bool((bits[:lo] == want).all()) and bool((bits[lo + fd.v.numel():] == want).all()) and n > 0
+
+
+def amax_word_check(word, expect, what):
+    """An amax word (a CPU tensor of AMAX_FLOATS): the maximum over its 16 slots is `expect` exactly, nothing lies between them."""
+    slots = word[::AMAX_STRIDE]
+    assert float(slots.max()) == expect, f'{what}: amax word {float(slots.max())} != max |out| {expect}'
+    rest = word.clone()
+    rest[::AMAX_STRIDE] = 0
+    assert not bool(rest.any()), f'{what}: amax word written between its slots'
+
+
+# ----------------------------------------------------------------------------------------------- the a-priori bound
+def rep_of(split):
+    """Representation: |v - hi - lo| <= 2**-22 |v| on either operand and the dropped lo*lo; plain fp16: 2**-11 on either."""
+    return 3 * 2.0 ** -22 if split == 2 else 2 * 2.0 ** -11
+
+
+def bound_terms(S, wn, add, K, R, rep):
+    """Representation, values below the exponent window, and fp32 accumulation of K terms with R further roundings, on
+    S = sum |terms| (+ `add`: what a tail adds); the callers add the partial sums of split-K and one ulp of the result."""
+    return rep * S + 2.0 ** -27 * wn + (K + R) * 2.0 ** -24 * (S + add)
+
+
+def split_halves(v, lo=True):
+    """The documented split on the CPU with ONE exponent for the tensor (maximum placed in [4, 8), as CV_EXP_TARGET = 2):
+    hi = fp16(v * 2^e), lo = fp16(v * 2^e - hi) (zero with lo = False) -> (hi, lo, 2^-e), fp64."""
+    e = 2 - math.floor(math.log2(float(v.abs().max())))
+    w = v.float() * 2.0 ** e
+    hi = w.half()
+    lw = (w - hi.float()).half() if lo else torch.zeros_like(hi)
+    return hi.double(), lw.double(), 2.0 ** -e
 
 
 def split_image(tn):

@@ -69,7 +69,7 @@ Forms no geometry under the size cap reaches (production build; no case): <2,vec
 RICK_U9_* / RICK_IGEMM_NOUNROLL / RICK_CONV_DEBUG arms exist in the experiment build only.  <2,vec,NJ4,NT9,WDMA0> needs
 lds + 16 KB > 80 KB at NPP <= 192, that is nbe * cps >= 57; with one image per tile that is 58 chunks per block without
 split-K, out of reach, but five images per 4 x 4 tile reach it at cps = 14 (Ci = 7 168, 16 splits): it has a case.
-rick_convt2_f32 (convt2.hip) has its own plan and position map and is out of scope: it deserves a forms test of its own.
+rick_convt2_f32 (convt2.hip) has its own plan and position map: tests/test_gpu_convt2_forms.py holds its forms to the same checks.
 """
 import contextlib
 import ctypes
@@ -81,8 +81,9 @@ import pytest
 import torch
 
 from rick_amd.synth import synth_tensor
-from tests.forms_common import (AMAX_FLOATS, AMAX_STRIDE, DEV, SENT, Fenced, Guarded, _gen, cdiv, f32, fenced, fine, ilog2_ceil, ints,
-                                p, sat_count, scales, split_image, stream)
+from tests.forms_common import (AMAX_FLOATS, AMAX_STRIDE, DEV, SENT, Fenced, Guarded, _gen, amax_word_check, bound_terms, cdiv, f32,
+                                fenced, fine, ilog2_ceil, ints, nan_fence_ok, p, rep_of, sat_count, scales, split_halves, split_image,
+                                stream)
 
 gpu = pytest.mark.gpu
 EINVAL = 22
@@ -643,10 +644,10 @@ def _reference(key):
             S = b.alpha * (osc if b.osc is None else osc.abs()) * contract(g, b.X.abs(), b.W.abs())
             sw = torch.stack([b.W.abs()[:, :, g.wt[t]].sum(1) for t in range(g.ntaps)]).sum(0)            # [Co]
             wn = b.alpha * (osc if b.osc is None else osc.abs()) * (float(b.X.abs().max()) * sw + float(b.W.abs().max()) * taps_sum(g, b.X.abs())[..., None])
-            rep = 3 * 2.0 ** -22 if g.split == 2 else 2 * 2.0 ** -11
+            rep = rep_of(g.split)
             r.rep = rep
             gain = float(b.gain) if b.act else 1.0
-            r.bnd[sl] = (rep * S + 2.0 ** -27 * wn + (g.Ci * g.ntaps + R_ROUND) * 2.0 ** -24 * (S + add)) * gain
+            r.bnd[sl] = bound_terms(S, wn, add, g.Ci * g.ntaps, R_ROUND, rep) * gain
             t4 = make_tiling(g, tile_positions(g))
             plan_split(t4, g.ntaps)
             r.per_split[sl] = (t4.nsplit if t4.nsplit > 1 else 0) * 2.0 ** -24 * (S + add) * gain        # (not on the eight-wave forms: one split)
@@ -666,15 +667,9 @@ def bound_of(r, w8=False):
 def emulate(c, b, lo=True):
     """The documented split on the CPU with ONE exponent per operand (maximum placed in [4, 8), as CV_EXP_TARGET = 2):
     hi = fp16(v * 2^e), lo = fp16(v * 2^e - hi), products hi*hi + hi*lo + lo*hi (no lo*lo), summed in fp64; no tail."""
-    def halves(v):
-        e = 2 - math.floor(math.log2(float(v.abs().max())))
-        w = v.float() * 2.0 ** e
-        hi = w.half()
-        lw = (w - hi.float()).half() if lo and c.split == 2 else torch.zeros_like(hi)
-        return hi.double(), lw.double(), 2.0 ** -e
     g = b.gs[0]
-    xh, xl, ux = halves(b.X)
-    wh, wl, uw = halves(b.W)
+    xh, xl, ux = split_halves(b.X, lo and c.split == 2)
+    wh, wl, uw = split_halves(b.W, lo and c.split == 2)
     osc = b.osc.double()[:, None, None, :] if b.osc is not None else 1.0
     return b.alpha * osc * ux * uw * (contract(g, xh, wh) + contract(g, xh, wl) + contract(g, xl, wh))
 
@@ -809,15 +804,6 @@ def test_exact_inputs_fit_and_the_bound_sees_a_lost_lo_half_where_it_can():
 
 
 # ----------------------------------------------------------------------------------------------------- device helpers
-def nan_fence_ok(fd):
-    """The bands of a Fenced buffer still hold what they were filled with (a view the device writes: the packed weight)."""
-    n = fd.buf.numel() - fd.v.numel()
-    lo = fd.v.data_ptr() - fd.buf.data_ptr() >> 2
-    bits = fd.buf.view(torch.int32)
-    want = bits[0].item()
-    return bool((bits[:lo] == want).all()) and bool((bits[lo + fd.v.numel():] == want).all()) and n > 0
-
-
 def pack_weight(c, b):
     from rick_amd._lib import lib
     g = b.gs[0]
@@ -931,12 +917,7 @@ def check_result(c, mode, b, r, rf, got):
         print(f'{c.id}: max |err| / bound = {worst:.4f} (K = {b.K}, nsplit = {r.nsplit})')
         assert bool((err <= bnd).all()), f'{c.id}: |err| up to {worst:.3f} x the a-priori bound'
     if c.amax:
-        w = got.word.v.detach().cpu()
-        slots = w[::AMAX_STRIDE]
-        assert float(slots.max()) == float(dev[rf.named].abs().max()), f'{c.id}: amax word {float(slots.max())} != max |out| {float(dev[rf.named].abs().max())}'
-        rest = w.clone()
-        rest[::AMAX_STRIDE] = 0
-        assert not bool(rest.any()), f'{c.id}: amax word written between its slots'
+        amax_word_check(got.word.v.detach().cpu(), float(dev[rf.named].abs().max()), c.id)
     if c.so:
         from rick_amd._lib import lib
         hdr = got.hdr.v.detach().cpu()
