@@ -43,6 +43,21 @@ int rick_upfirdn2d_f32(const float *input, const float *kernel, float *out,
                        int64_t major, int in_h, int in_w, int minor, int kh, int kw,
                        int up_x, int up_y, int down_x, int down_y,
                        int pad_x0, int pad_x1, int pad_y0, int pad_y1, void *stream);
+/* Layouts: minor == 1 (planar [major, H, W]; 4-byte accesses only, any float alignment) or channels-last with minor in
+ * {4, 8, ..., 64} or minor % 64 == 0; anything else is RICK_EINVAL.  Every channels-last kernel makes 16-byte accesses: `input`,
+ * `out`, and with rick_upfirdn2d_ex_f32 `chan_scale` and the split image, must be 16-byte aligned there, RICK_EINVAL otherwise
+ * (channels-last needs major <= 65535; planar takes any major, in slabs of 65535 planes).
+ * The form a call takes — host only, nothing is launched: out12 = {kernel (RICK_UFD_*), output tile h, w, staged input window
+ * h, w, LDS bytes per block, grid x, y, z, launches (> 1: the planar slab loop; grid y is then the first slab's), out_h, out_w}.
+ * has_tail / has_ex: a fused tail / the extended result handling is asked for; aligned16: the pointers named above are
+ * 16-byte aligned.  Returns what the launch would return for the geometry (RICK_EINVAL: no kernel takes it). */
+#define RICK_UFD_K4_T8 0      /* 4x4 taps, up 1, down 1: 8 x 8 outputs x 64 channels per block */
+#define RICK_UFD_K4_T16 1     /* the same on 16 x 16 outputs x 32 channels (RICK_TUNE_UFD_TILE16) */
+#define RICK_UFD_K4_D2 2      /* 4x4 taps, up 1, down 2: 4 x 8 outputs x 64 channels */
+#define RICK_UFD_NHWC 3       /* generic channels-last: the largest tile whose staged window fits 60 KB of LDS */
+#define RICK_UFD_PLANAR 4     /* generic planar */
+int rick_upfirdn2d_plan(int64_t major, int in_h, int in_w, int minor, int kh, int kw, int up_x, int up_y, int down_x, int down_y,
+                        int pad_x0, int pad_x1, int pad_y0, int pad_y1, int has_tail, int has_ex, int aligned16, int *out12);
 
 /* The same operator in the reference's other dtypes (op/upfirdn2d_kernel.cu:311-367 dispatches half / float / double):
  * dtype 1 = float64, 2 = float16 (fp32 accumulation); planar [major, H, W] layout (minor == 1), kernel taps in the same
@@ -186,7 +201,9 @@ int rick_conv_igemm_f32(const float *x, const void *packed_w, float *out,
                         const float *iscale, const float *oscale,
                         const rick_conv_geom *g, void *workspace, void *stream);
 /* rick_upfirdn2d_f32 with the same tail fused after the FIR (the blur that follows every upsampling StyledConv,
- * model_probe_tune.py:263-268,344-348): channels-last 4x4 taps, up = 1, minor % 64 == 0 only (else non-zero). */
+ * model_probe_tune.py:263-268,344-348): channels-last 4x4 taps, up = 1, minor % 64 == 0 only (else non-zero).  The FIR takes the
+ * tail's bias / noise / activation fields; its amax / split_out fields must be NULL (RICK_EINVAL otherwise): the FIR's own result
+ * handling is rick_split_out (rick_upfirdn2d_ex_f32). */
 int rick_upfirdn2d_act_f32(const float *input, const float *kernel, float *out,
                            int64_t major, int in_h, int in_w, int minor, int kh, int kw,
                            int up_x, int up_y, int down_x, int down_y,

@@ -113,6 +113,7 @@ SIGNATURES = {
                                           c_fp, c_fp]),
     'rick_convt2_split_f32': (c_int, [c_fp, c_fp, c_fp, c_fp, c_fp] + [c_int] * 7 + [c_f, c_fp, c_fp, c_fp]),
     'rick_upfirdn2d_adjoint_rows': (c_i64, [c_i64, c_int, c_int]),
+    'rick_upfirdn2d_plan': (c_int, [c_i64] + [c_int] * 16 + [ctypes.POINTER(c_int)]),
     'rick_colsum_f32': (c_int, [c_fp, c_fp, c_i64, c_int, c_int, c_int, c_fp]),
     'rick_bound_tail_f32': (c_int, [c_fp, c_fp, c_f, c_fp, c_fp, c_fp, c_int, c_f, c_fp, c_int, c_fp]),
     'rick_bias_act_bwd_split2_f32': (c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_f, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_i64,

@@ -355,6 +355,109 @@ static int upfirdn2d_impl(const float *input, const float *kernel, float *out, i
 // 16 x 16 output tiles for the 4x4 up = 1 down = 1 form (rick_conv_tuning RICK_TUNE_UFD_TILE16; outputs of >= 32 x 32)
 static bool ufd_tile16(int out_h, int out_w) { return rick_internal_tune(RICK_TUNE_UFD_TILE16) && out_h >= 32 && out_w >= 32; }
 
+// Every dispatch decision of a launch, taken on the host from the geometry alone: the launcher below and rick_upfirdn2d_plan
+// (what the tests hold their replay to) both consume it.  `aligned16`: input, out (the split image when out is NULL) and
+// chan_scale are 16-byte aligned — every channels-last kernel makes float4 accesses at them.
+enum { UFD_K4_T8 = RICK_UFD_K4_T8, UFD_K4_T16 = RICK_UFD_K4_T16, UFD_K4_D2 = RICK_UFD_K4_D2, UFD_NHWC = RICK_UFD_NHWC, UFD_PLANAR = RICK_UFD_PLANAR };
+struct UfdPlan {
+    int kernel;              // UFD_*
+    int toh, tow, tih, tiw;  // output tile, staged input window
+    int lds;                 // bytes of LDS per block (4x4 forms: static)
+    int grid_x, grid_y, grid_z;
+    int launches;            // > 1: the planar slab loop (grid_y is then the first slab's, 65535)
+    int out_h, out_w;
+    int cb4, tiles_x;
+};
+
+static int ufd_plan(int64_t major, int in_h, int in_w, int minor, int kh, int kw, int up_x, int up_y, int down_x, int down_y,
+                    int pad_x0, int pad_x1, int pad_y0, int pad_y1, bool has_tail, bool has_ex, bool aligned16, UfdPlan *pl) {
+    if (major <= 0 || in_h <= 0 || in_w <= 0 || minor <= 0 || kh <= 0 || kw <= 0 || up_x <= 0 || up_y <= 0 || down_x <= 0 || down_y <= 0)
+        return RICK_EINVAL;
+    pl->out_h = (in_h * up_y + pad_y0 + pad_y1 - kh) / down_y + 1;
+    pl->out_w = (in_w * up_x + pad_x0 + pad_x1 - kw) / down_x + 1;
+    if (pl->out_h <= 0 || pl->out_w <= 0) return RICK_EINVAL;
+    pl->launches = 1;
+    pl->grid_z = 1;
+    pl->cb4 = 0;
+    if (minor % 64 == 0 && kh == 4 && kw == 4 && up_x == 1 && up_y == 1 && down_x == down_y && (down_x == 1 || down_x == 2) &&
+        major <= 65535 && minor / 64 <= 65535 && aligned16) {
+        if (down_x == 1 && ufd_tile16(pl->out_h, pl->out_w)) {        // 16 x 16 tile on 32-channel slabs (see the kernel's comment)
+            if (2 * (int64_t)(minor / 64) > 65535) return RICK_EINVAL;
+            pl->kernel = UFD_K4_T16; pl->toh = 16; pl->tow = 16; pl->cb4 = 8;
+        } else if (down_x == 1) {
+            pl->kernel = UFD_K4_T8; pl->toh = 8; pl->tow = 8; pl->cb4 = 16;
+        } else {
+            pl->kernel = UFD_K4_D2; pl->toh = 4; pl->tow = 8; pl->cb4 = 16;
+        }
+        pl->tih = (pl->toh - 1) * down_y + 4;
+        pl->tiw = (pl->tow - 1) * down_x + 4;
+        pl->lds = pl->tih * pl->tiw * pl->cb4 * 16;
+        pl->tiles_x = cdiv(pl->out_w, pl->tow);
+        pl->grid_x = pl->tiles_x * cdiv(pl->out_h, pl->toh);
+        pl->grid_y = minor / (pl->cb4 * 4);
+        pl->grid_z = (int)major;
+        return 0;
+    }
+    if (has_tail) return RICK_EINVAL;   // the fused tail exists on the channels-last 4x4 path only
+    const bool nhwc = minor % 4 == 0 && minor % (((minor >= 64 ? 64 : minor) / 4) * 4) == 0;
+    if (minor % 4 == 0 && !nhwc) return RICK_EINVAL;   // minor > 64 that is no multiple of 64 (e.g. 72): no kernel takes it
+    if (nhwc) {
+        if (!aligned16) return RICK_EINVAL;            // float4 loads / stores at input, out, chan_scale and the split image
+        const int cb4 = (minor >= 64 ? 64 : minor) / 4;
+        int toh = 8, tow = 8;
+        for (;;) {
+            pl->toh = toh; pl->tow = tow;
+            pl->tih = tile_in_extent(toh, down_y, kh, up_y);
+            pl->tiw = tile_in_extent(tow, down_x, kw, up_x);
+            size_t lds = (size_t)((kh * kw + 3) & ~3) * 4 + (size_t)pl->tih * pl->tiw * cb4 * 16;
+            if (lds <= 60 * 1024 || (toh == 1 && tow == 1)) {
+                if (lds > 64 * 1024) return RICK_EINVAL;
+                if (major > 65535 || minor / (cb4 * 4) > 65535) return RICK_EINVAL;
+                pl->kernel = UFD_NHWC; pl->cb4 = cb4; pl->lds = (int)lds;
+                pl->tiles_x = cdiv(pl->out_w, tow);
+                pl->grid_x = pl->tiles_x * cdiv(pl->out_h, toh);
+                pl->grid_y = minor / (cb4 * 4);
+                pl->grid_z = (int)major;
+                return 0;
+            }
+            if (toh >= tow && toh > 1) toh >>= 1; else tow >>= 1;
+        }
+    }
+    if (has_ex) return RICK_EINVAL;       // the extended result handling exists on the channels-last kernels only
+    if (minor != 1) return RICK_EINVAL;   // callers re-layout to planar or channels-last x4
+    int toh = 16, tow = 64;
+    for (;;) {
+        pl->toh = toh; pl->tow = tow;
+        pl->tih = tile_in_extent(toh, down_y, kh, up_y);
+        pl->tiw = tile_in_extent(tow, down_x, kw, up_x);
+        size_t lds = (size_t)(kh * kw + pl->tih * pl->tiw) * 4;
+        if (lds <= 60 * 1024 || (toh == 1 && tow == 1)) {
+            if (lds > 64 * 1024) return RICK_EINVAL;
+            pl->kernel = UFD_PLANAR; pl->lds = (int)lds;
+            pl->tiles_x = cdiv(pl->out_w, tow);
+            pl->grid_x = pl->tiles_x * cdiv(pl->out_h, toh);
+            // grid.y carries `major` (N*C); very large majors go in slabs of 65535 planes
+            pl->grid_y = (int)(major > 65535 ? 65535 : major);
+            pl->launches = (int)((major + 65534) / 65535);
+            return 0;
+        }
+        if (toh >= tow && toh > 1) toh >>= 1; else tow >>= 1;
+    }
+}
+
+extern "C" int rick_upfirdn2d_plan(int64_t major, int in_h, int in_w, int minor, int kh, int kw, int up_x, int up_y, int down_x,
+                                   int down_y, int pad_x0, int pad_x1, int pad_y0, int pad_y1, int has_tail, int has_ex,
+                                   int aligned16, int *out12) {
+    if (!out12) return RICK_EINVAL;
+    UfdPlan pl;
+    const int rc = ufd_plan(major, in_h, in_w, minor, kh, kw, up_x, up_y, down_x, down_y, pad_x0, pad_x1, pad_y0, pad_y1, has_tail != 0,
+                            has_ex != 0, aligned16 != 0, &pl);
+    if (rc) return rc;
+    const int v[12] = {pl.kernel, pl.toh, pl.tow, pl.tih, pl.tiw, pl.lds, pl.grid_x, pl.grid_y, pl.grid_z, pl.launches, pl.out_h, pl.out_w};
+    for (int i = 0; i < 12; i++) out12[i] = v[i];
+    return 0;
+}
+
 extern "C" int rick_upfirdn2d_f32(const float *input, const float *kernel, float *out,
                                   int64_t major, int in_h, int in_w, int minor, int kh, int kw,
                                   int up_x, int up_y, int down_x, int down_y,
@@ -391,106 +494,57 @@ extern "C" int rick_upfirdn2d_ex_f32(const float *input, const float *kernel, fl
                           down_y, pad_x0, pad_x1, pad_y0, pad_y1, tail, stream, ex);
 }
 
+template <int DOWN, int TOH, int TOW, int CB4>
+static void ufd_launch_k4(dim3 grid, hipStream_t st, const float *input, const float *kernel, float *out, const UfdParams &p,
+                          const rick_conv_epilogue *tail, const rick_split_out *xo) {
+    const rick_conv_epilogue none = {nullptr, nullptr, nullptr, 1, 0, 0.f, 1.f, nullptr, nullptr, nullptr, nullptr, 1.f, nullptr};
+    if (xo && tail) hipLaunchKernelGGL((upfirdn2d_nhwc_k4_kernel<DOWN, TOH, TOW, true, true, CB4>), grid, dim3(256), 0, st, input, kernel, out, p, *tail, *xo);
+    else if (xo) hipLaunchKernelGGL((upfirdn2d_nhwc_k4_kernel<DOWN, TOH, TOW, false, true, CB4>), grid, dim3(256), 0, st, input, kernel, out, p, none, *xo);
+    else if (tail) hipLaunchKernelGGL((upfirdn2d_nhwc_k4_kernel<DOWN, TOH, TOW, true, false, CB4>), grid, dim3(256), 0, st, input, kernel, out, p, *tail, kNoSplitOut);
+    else hipLaunchKernelGGL((upfirdn2d_nhwc_k4_kernel<DOWN, TOH, TOW, false, false, CB4>), grid, dim3(256), 0, st, input, kernel, out, p, none, kNoSplitOut);
+}
+
 static int upfirdn2d_impl(const float *input, const float *kernel, float *out, int64_t major, int in_h, int in_w, int minor,
                           int kh, int kw, int up_x, int up_y, int down_x, int down_y, int pad_x0, int pad_x1, int pad_y0,
                           int pad_y1, const rick_conv_epilogue *tail, void *stream, const rick_split_out *xo) {
-    if (!input || !kernel || !out || major <= 0 || in_h <= 0 || in_w <= 0 || minor <= 0 || kh <= 0 ||
-        kw <= 0 || up_x <= 0 || up_y <= 0 || down_x <= 0 || down_y <= 0)
-        return RICK_EINVAL;
+    if (!input || !kernel || !out) return RICK_EINVAL;
+    // a fused tail carries bias / noise / activation only: its amax / split_out fields belong to the convolution's epilogue
+    // (the FIR's own are in rick_split_out)
+    if (tail && (tail->amax || tail->split_out)) return RICK_EINVAL;
+    const bool aligned16 = (((uintptr_t)input | (uintptr_t)out | (uintptr_t)(xo ? xo->chan_scale : nullptr)) % 16) == 0;
+    UfdPlan pl;
+    const int rc = ufd_plan(major, in_h, in_w, minor, kh, kw, up_x, up_y, down_x, down_y, pad_x0, pad_x1, pad_y0, pad_y1, tail != nullptr,
+                            xo != nullptr, aligned16, &pl);
+    if (rc) return rc;
     UfdParams p;
     p.in_h = in_h; p.in_w = in_w; p.minor = minor; p.kh = kh; p.kw = kw;
     p.up_x = up_x; p.up_y = up_y; p.down_x = down_x; p.down_y = down_y;
     p.pad_x0 = pad_x0; p.pad_y0 = pad_y0;
-    p.out_h = (in_h * up_y + pad_y0 + pad_y1 - kh) / down_y + 1;
-    p.out_w = (in_w * up_x + pad_x0 + pad_x1 - kw) / down_x + 1;
-    if (p.out_h <= 0 || p.out_w <= 0) return RICK_EINVAL;
+    p.out_h = pl.out_h; p.out_w = pl.out_w;
+    p.toh = pl.toh; p.tow = pl.tow; p.tih = pl.tih; p.tiw = pl.tiw; p.tiles_x = pl.tiles_x;
     hipStream_t st = (hipStream_t)stream;
-    if (minor % 64 == 0 && kh == 4 && kw == 4 && up_x == 1 && up_y == 1 && down_x == down_y && (down_x == 1 || down_x == 2) &&
-        major <= 65535 && minor / 64 <= 65535 && (((uintptr_t)input | (uintptr_t)out) % 16 == 0)) {
-        const rick_conv_epilogue none = {nullptr, nullptr, nullptr, 1, 0, 0.f, 1.f, nullptr, nullptr, nullptr, nullptr, 1.f, nullptr};
+    const dim3 grid(pl.grid_x, pl.grid_y, pl.grid_z);
+    if (pl.kernel == UFD_K4_T8 || pl.kernel == UFD_K4_T16 || pl.kernel == UFD_K4_D2) {
         if (tail) {
             if (tail->noise && (!tail->noise_w || (tail->noise_nb != 1 && tail->noise_nb != major))) return RICK_EINVAL;
             if (tail->bias && ((uintptr_t)tail->bias % 16)) return RICK_EINVAL;
         }
-        if (down_x == 1 && ufd_tile16(p.out_h, p.out_w)) {        // 16 x 16 tile on 32-channel slabs (see the kernel's comment)
-            if (2 * (int64_t)(minor / 64) > 65535) return RICK_EINVAL;
-            p.tiles_x = cdiv(p.out_w, 16);
-            dim3 grid(p.tiles_x * cdiv(p.out_h, 16), minor / 32, (unsigned)major);
-            if (xo && tail) hipLaunchKernelGGL((upfirdn2d_nhwc_k4_kernel<1, 16, 16, true, true, 8>), grid, dim3(256), 0, st, input, kernel, out, p, *tail, *xo);
-            else if (xo) hipLaunchKernelGGL((upfirdn2d_nhwc_k4_kernel<1, 16, 16, false, true, 8>), grid, dim3(256), 0, st, input, kernel, out, p, none, *xo);
-            else if (tail) hipLaunchKernelGGL((upfirdn2d_nhwc_k4_kernel<1, 16, 16, true, false, 8>), grid, dim3(256), 0, st, input, kernel, out, p, *tail, kNoSplitOut);
-            else hipLaunchKernelGGL((upfirdn2d_nhwc_k4_kernel<1, 16, 16, false, false, 8>), grid, dim3(256), 0, st, input, kernel, out, p, none, kNoSplitOut);
-        } else if (down_x == 1) {
-            p.tiles_x = cdiv(p.out_w, 8);
-            dim3 grid(p.tiles_x * cdiv(p.out_h, 8), minor / 64, (unsigned)major);
-            if (xo && tail) hipLaunchKernelGGL((upfirdn2d_nhwc_k4_kernel<1, 8, 8, true, true>), grid, dim3(256), 0, st, input, kernel, out, p, *tail, *xo);
-            else if (xo) hipLaunchKernelGGL((upfirdn2d_nhwc_k4_kernel<1, 8, 8, false, true>), grid, dim3(256), 0, st, input, kernel, out, p, none, *xo);
-            else if (tail) hipLaunchKernelGGL((upfirdn2d_nhwc_k4_kernel<1, 8, 8, true>), grid, dim3(256), 0, st, input, kernel, out, p, *tail, kNoSplitOut);
-            else hipLaunchKernelGGL((upfirdn2d_nhwc_k4_kernel<1, 8, 8, false>), grid, dim3(256), 0, st, input, kernel, out, p, none, kNoSplitOut);
-        } else {
-            p.tiles_x = cdiv(p.out_w, 8);
-            dim3 grid(p.tiles_x * cdiv(p.out_h, 4), minor / 64, (unsigned)major);
-            if (xo && tail) hipLaunchKernelGGL((upfirdn2d_nhwc_k4_kernel<2, 4, 8, true, true>), grid, dim3(256), 0, st, input, kernel, out, p, *tail, *xo);
-            else if (xo) hipLaunchKernelGGL((upfirdn2d_nhwc_k4_kernel<2, 4, 8, false, true>), grid, dim3(256), 0, st, input, kernel, out, p, none, *xo);
-            else if (tail) hipLaunchKernelGGL((upfirdn2d_nhwc_k4_kernel<2, 4, 8, true>), grid, dim3(256), 0, st, input, kernel, out, p, *tail, kNoSplitOut);
-            else hipLaunchKernelGGL((upfirdn2d_nhwc_k4_kernel<2, 4, 8, false>), grid, dim3(256), 0, st, input, kernel, out, p, none, kNoSplitOut);
-        }
+        if (pl.kernel == UFD_K4_T16) ufd_launch_k4<1, 16, 16, 8>(grid, st, input, kernel, out, p, tail, xo);
+        else if (pl.kernel == UFD_K4_T8) ufd_launch_k4<1, 8, 8, 16>(grid, st, input, kernel, out, p, tail, xo);
+        else ufd_launch_k4<2, 4, 8, 16>(grid, st, input, kernel, out, p, tail, xo);
         RICK_LAUNCH_STATUS();
     }
-    if (tail) return RICK_EINVAL;   // the fused tail exists on the channels-last 4x4 path only
-    if (minor % 4 == 0) {
-        const int cb4 = (minor >= 64 ? 64 : minor) / 4;
-        if (minor % (cb4 * 4) != 0) goto planar_like;    // e.g. minor = 72: fall through to generic
-        int toh = 8, tow = 8;
-        for (;;) {
-            p.toh = toh; p.tow = tow;
-            p.tih = tile_in_extent(toh, down_y, kh, up_y);
-            p.tiw = tile_in_extent(tow, down_x, kw, up_x);
-            size_t lds = (size_t)((kh * kw + 3) & ~3) * 4 + (size_t)p.tih * p.tiw * cb4 * 16;
-            if (lds <= 60 * 1024 || (toh == 1 && tow == 1)) {
-                if (lds > 64 * 1024) return RICK_EINVAL;
-                p.tiles_x = cdiv(p.out_w, tow);
-                if (major > 65535 || minor / (cb4 * 4) > 65535) return RICK_EINVAL;
-                dim3 grid(p.tiles_x * cdiv(p.out_h, toh), minor / (cb4 * 4), (unsigned)major);
-                if (xo) hipLaunchKernelGGL(upfirdn2d_nhwc_kernel<true>, grid, dim3(256), lds, st, input, kernel, out, p, cb4, *xo);
-                else hipLaunchKernelGGL(upfirdn2d_nhwc_kernel<false>, grid, dim3(256), lds, st, input, kernel, out, p, cb4, kNoSplitOut);
-                RICK_LAUNCH_STATUS();
-            }
-            if (toh >= tow && toh > 1) toh >>= 1; else tow >>= 1;
-        }
+    if (pl.kernel == UFD_NHWC) {
+        if (xo) hipLaunchKernelGGL(upfirdn2d_nhwc_kernel<true>, grid, dim3(256), pl.lds, st, input, kernel, out, p, pl.cb4, *xo);
+        else hipLaunchKernelGGL(upfirdn2d_nhwc_kernel<false>, grid, dim3(256), pl.lds, st, input, kernel, out, p, pl.cb4, kNoSplitOut);
+        RICK_LAUNCH_STATUS();
     }
-planar_like:
-    if (xo) return RICK_EINVAL;           // the extended result handling exists on the channels-last kernels only
-    if (minor != 1) return RICK_EINVAL;   // callers re-layout to planar or channels-last x4
-    {
-        int toh = 16, tow = 64;
-        for (;;) {
-            p.toh = toh; p.tow = tow;
-            p.tih = tile_in_extent(toh, down_y, kh, up_y);
-            p.tiw = tile_in_extent(tow, down_x, kw, up_x);
-            size_t lds = (size_t)(kh * kw + p.tih * p.tiw) * 4;
-            if (lds <= 60 * 1024 || (toh == 1 && tow == 1)) {
-                if (lds > 64 * 1024) return RICK_EINVAL;
-                p.tiles_x = cdiv(p.out_w, tow);
-                // grid.y carries `major` (N*C); split very large majors over grid.z-free loop
-                if (major > 65535 * 1LL) {
-                    // launch in slabs of 65535 planes
-                    for (int64_t m0 = 0; m0 < major; m0 += 65535) {
-                        int64_t mm = major - m0 < 65535 ? major - m0 : 65535;
-                        dim3 grid(p.tiles_x * cdiv(p.out_h, toh), (unsigned)mm);
-                        hipLaunchKernelGGL(upfirdn2d_planar_kernel, grid, dim3(256), lds, st,
-                                           input + m0 * (int64_t)in_h * in_w, kernel,
-                                           out + m0 * (int64_t)p.out_h * p.out_w, p);
-                    }
-                    RICK_LAUNCH_STATUS();
-                }
-                dim3 grid(p.tiles_x * cdiv(p.out_h, toh), (unsigned)major);
-                hipLaunchKernelGGL(upfirdn2d_planar_kernel, grid, dim3(256), lds, st, input, kernel, out, p);
-                RICK_LAUNCH_STATUS();
-            }
-            if (toh >= tow && toh > 1) toh >>= 1; else tow >>= 1;
-        }
+    for (int64_t m0 = 0; m0 < major; m0 += 65535) {       // planar: one launch, or slabs of 65535 planes
+        const int64_t mm = major - m0 < 65535 ? major - m0 : 65535;
+        hipLaunchKernelGGL(upfirdn2d_planar_kernel, dim3(pl.grid_x, (unsigned)mm), dim3(256), pl.lds, st,
+                           input + m0 * (int64_t)in_h * in_w, kernel, out + m0 * (int64_t)pl.out_h * pl.out_w, p);
     }
+    RICK_LAUNCH_STATUS();
 }
 
 CV_DEFINE_SAT_ACCESSOR(rick_sat_upfirdn2d)

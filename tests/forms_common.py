@@ -1,5 +1,5 @@
-"""What the kernel-forms tests share (test_gpu_wgrad_forms.py, test_gpu_igemm_forms.py, test_gpu_convt2_forms.py): guarded and
-fenced device buffers, the integer / 12-bit / scale generators of the exact modes, split images, the saturation counter, the
+"""What the kernel-forms tests share (test_gpu_wgrad_forms.py, test_gpu_igemm_forms.py, test_gpu_convt2_forms.py,
+test_gpu_ufd_forms.py): guarded and fenced device buffers, the integer / 12-bit / scale generators of the exact modes, split images, the saturation counter, the
 NaN-fence and amax-word checks, the terms of the a-priori bound.  A plain module: no fixtures, no pytest hooks."""
 import ctypes
 import math
@@ -152,6 +152,12 @@ def split_halves(v, lo=True):
     hi = w.half()
     lw = (w - hi.float()).half() if lo else torch.zeros_like(hi)
     return hi.double(), lw.double(), 2.0 ** -e
+
+
+def decode_image(img, hdr):
+    """A split image (CPU, viewed as fp32) and its header -> the values it holds, (hi + lo) * 2^-e, flat."""
+    h = img.view(torch.float16).reshape(-1, 8).float()
+    return ((h[:, :4] + h[:, 4:]) * hdr[1]).reshape(-1)
 
 
 def split_image(tn):

@@ -81,8 +81,8 @@ import pytest
 import torch
 
 from rick_amd.synth import synth_tensor
-from tests.forms_common import (AMAX_FLOATS, AMAX_STRIDE, DEV, SENT, Fenced, Guarded, _gen, amax_word_check, bound_terms, cdiv, f32,
-                                fenced, fine, ilog2_ceil, ints, nan_fence_ok, p, rep_of, sat_count, scales, split_halves, split_image,
+from tests.forms_common import (AMAX_FLOATS, AMAX_STRIDE, DEV, SENT, Fenced, Guarded, _gen, amax_word_check, bound_terms, cdiv,
+                                decode_image, f32, fenced, fine, ilog2_ceil, ints, nan_fence_ok, p, rep_of, sat_count, scales, split_halves, split_image,
                                 stream)
 
 gpu = pytest.mark.gpu
@@ -873,11 +873,6 @@ def launch(c, b, o, out, ws, epi, bad=''):
     if epi is None:
         return lib.rick_conv_igemm_f32(p(o.x), p(o.w), outp, p(o.isc), p(o.osc), ctypes.byref(gs[0]), wsp, stream())
     return lib.rick_conv_igemm_act_f32(p(o.x), p(o.w), outp, p(o.isc), p(o.osc), ctypes.byref(gs[0]), ep, wsp, stream())
-
-
-def decode_image(img, hdr):
-    h = img.view(torch.float16).reshape(-1, 8).float()
-    return ((h[:, :4] + h[:, 4:]) * hdr[1]).reshape(-1)
 
 
 def run_once(c, b, o, r, tune):
