@@ -914,6 +914,43 @@ int rick_svd_grad_f32(const float *grad, int64_t n, const float *u, int64_t nu, 
 int rick_svd_grad_finish_f32(const float *partials, int64_t npart, float *dd, int64_t nd, const rick_svd_layer *layers,
                              const rick_svd_layer *layers_host, int nlayers, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Patch head — the head of CDC's patch-level discriminator (rick_amd/patchd.py): ConvLayer(C, 1, 3) of the reference
+ * (model_probe_tune.py:595-641: EqualConv2d :101-136 + FusedLeakyReLU, op/fused_act.py:73-82) on a tapped feature map, as thin
+ * HBM-bound kernels instead of an implicit GEMM with one live output column.  x is the map in channels-last memory [N][H][W][C],
+ * w the weight [1][C][3][3] (w[c][t] at 9 c + t, t = 3 ky + kx), b the bias [1] in DEVICE memory, out / g the logit map and its
+ * gradient [N][H][W]:
+ *   z[n,y,x]    = b + sum_c sum_t (wscale w[c,t]) X[n,c,y+ky-1,x+kx-1]          (zero outside; correlation, as F.conv2d)
+ *   out         = gain (z > 0 ? z : slope z)
+ *   gz          = g gain (out > 0 ? 1 : slope)          (the sign of the STORED output, as fused_act's backward takes it)
+ *   gb          = sum gz
+ *   gw[c,t]     = wscale sum_{n,y,x} gz[n,y,x] X[n,c,y+ky-1,x+kx-1]
+ *   gX[n,c,u,v] = sum_t (wscale w[c,t]) gz[n,u-ky+1,v-kx+1]
+ * C % 4 == 0, 4 <= C <= 2048, N, H, W >= 1, N H W C < 2^31; x, w and gx 16-byte aligned, ws 8-byte, everything else 4-byte.
+ * rick_patch_head_fwd_f32: one launch, one wave per output pixel, 8 pixels per block.  Lane l owns the channels
+ *   4 l + 256 k + {0, 1, 2, 3}, k ascending, and keeps one fp32 fma chain per tap over them in that order (16-byte loads; the
+ *   9 C scaled weights are rounded once and staged per block in LDS); the lane adds its nine chains in ascending tap order (a tap
+ *   outside the image loads nothing and stays the chain's initial zero), the 32, 16, ..., 1 xor butterfly adds the lanes, then
+ *   b + sum.  The order is a function of C and the pixel's place in its own image: out[n] does not depend on N or on n.
+ * rick_patch_head_bwd_f32: one pass over x.  Block (slab, chunk) takes the pixels [slab L, (slab + 1) L) of the flattened
+ *   N H W map, L = 32 ceil(N H W / (32 * 512)) (at most 512 slabs), and the channels [256 chunk, 256 chunk + 256); lane l owns
+ *   four channels, wave v the pixels slab L + v + 4 k, k ascending.  gz of the nine neighbours of a pixel is formed from g and out
+ *   on the fly.  gx (may be NULL: not computed) = one fp32 chain over the taps ascending, (wscale w[c,0]) gz_0 first — gX[n]
+ *   depends on image n alone.  The weight and bias sums: one fp32 fma chain per (tap, channel) and wave over its pixels, the four
+ *   waves added ((w0 + w1) + w2) + w3 (the bias sum in fp64 throughout), into ws (rick_patch_head_workspace_bytes(N, H, W, C)
+ *   bytes, 8-byte aligned; -1 for sizes out of range): nslabs doubles of bias sums, then the floats [slab][t C + c].  Every
+ *   entry of ws is written.
+ * rick_patch_head_bwd_finish_f32: gw[c,t] = (float)(wscale * sum over the slabs, ascending, in fp64), gb = (float)(the same sum of
+ *   the bias partials).  The partition is a function of (N, H, W, C) alone; results are bit-identical from run to run.
+ * RICK_EINVAL, before any HIP call, for a null (but gx) or misaligned pointer, a size out of range, gx == x.
+ * No atomics, no host synchronisation, no allocation; every launch is on `stream`. */
+int64_t rick_patch_head_workspace_bytes(int N, int H, int W, int C);
+int rick_patch_head_fwd_f32(const float *x, const float *w, const float *b, float *out, int N, int H, int W, int C, float wscale,
+                            float slope, float gain, void *stream);
+int rick_patch_head_bwd_f32(const float *x, const float *w, const float *g, const float *out, float *gx, void *ws, int N, int H,
+                            int W, int C, float wscale, float slope, float gain, void *stream);
+int rick_patch_head_bwd_finish_f32(const void *ws, float *gw, float *gb, int N, int H, int W, int C, float wscale, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -229,6 +229,10 @@ SIGNATURES = {
     'rick_svd_apply_f32': (c_int, [c_fp, c_fp, c_i64, c_fp, c_i64, c_fp, c_i64, c_fp, c_i64, c_fp, c_fp, c_int, c_fp, c_int, c_fp]),
     'rick_svd_grad_f32': (c_int, [c_fp, c_i64, c_fp, c_i64, c_fp, c_i64, c_fp, c_i64, c_fp, c_fp, c_int, c_fp, c_int, c_fp]),
     'rick_svd_grad_finish_f32': (c_int, [c_fp, c_i64, c_fp, c_i64, c_fp, c_fp, c_int, c_fp]),
+    'rick_patch_head_workspace_bytes': (c_i64, [c_int] * 4),
+    'rick_patch_head_fwd_f32': (c_int, [c_fp] * 4 + [c_int] * 4 + [c_f] * 3 + [c_fp]),
+    'rick_patch_head_bwd_f32': (c_int, [c_fp] * 6 + [c_int] * 4 + [c_f] * 3 + [c_fp]),
+    'rick_patch_head_bwd_finish_f32': (c_int, [c_fp] * 3 + [c_int] * 4 + [c_f, c_fp]),
 }
 
 if not os.path.exists(LIB_PATH):

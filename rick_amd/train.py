@@ -224,6 +224,10 @@ class TrainConfig:
     dcl_batch: int = 4                               # CL1's own latent batch (like cdc_batch)
     svd_adapt: bool = False                          # FSGAN's singular-value adaptation of both networks (rick_amd/svd.py)
     svd_train_rest: bool = False                     # with svd_adapt: leave the non-adapted tensors (biases, ...) to the networks' Adam
+    subspace_freq: int = 0                           # CDC's patch discriminator + anchor sampling (rick_amd/patchd.py): every subspace_freq-th iteration is an anchor iteration, the others patch-level; 0 = off (the reference's --subspace_freq defaults to 4, :708)
+    subspace_std: float = 0.05                       # --subspace_std (:721)
+    feat_ind: int = 3                                # --feat_ind (:709): p_ind is drawn from the first feat_ind taps
+    n_anchors: int = 10                              # rows of the anchor matrix drawn at construction
 
 
 class AdaController:
@@ -325,9 +329,12 @@ class RickTrainer:
     or cfg.dcl_d_weight > 0; put in eval mode, gradients off); `d_source`: the frozen source discriminator of the discriminator
     contrastive term (required when cfg.dcl_d_weight > 0; treated like g_source).  `ewc`: the
     anchor of the elastic-weight-consolidation term (required when cfg.ewc_weight > 0), given as what `set_ewc` takes: a pair
-    (source_state, fisher) of {name: tensor} mappings, fisher None for the L2-SP penalty."""
+    (source_state, fisher) of {name: tensor} mappings, fisher None for the L2-SP penalty.  `patch_heads`: the
+    rick_amd.patchd.PatchHeads of CDC's patch-level discriminator (cfg.subspace_freq > 0; built here when None).  Deviation from
+    CDC as recalled: R1 stays on the image-level logits, where CDC sends it through the patch head on patch iterations."""
 
-    def __init__(self, cfg, generator, discriminator, g_ema, d_ema, dp=None, g_source=None, ewc=None, d_source=None):
+    def __init__(self, cfg, generator, discriminator, g_ema, d_ema, dp=None, g_source=None, ewc=None, d_source=None,
+                 patch_heads=None):
         self.cfg, self.g, self.d, self.g_ema, self.d_ema, self.dp = cfg, generator, discriminator, g_ema, d_ema, dp
         # the discriminator-side augmentation: DiffAugment (cfg.diffaug) or ADA (cfg.augment), never both; None when both are off
         self._augmenter = AdaAugmenter(self) if cfg.augment else None
@@ -374,6 +381,29 @@ class RickTrainer:
             src.eval()
             for p in src.parameters():
                 p.requires_grad = False
+        if isinstance(cfg.subspace_freq, bool) or not isinstance(cfg.subspace_freq, int) or cfg.subspace_freq < 0:
+            raise ValueError('RickTrainer: subspace_freq must be an integer >= 0')
+        if cfg.subspace_freq > 0:
+            from . import patchd
+            if dp is not None:
+                raise ValueError('RickTrainer: subspace_freq > 0 together with data parallelism (dp=) is not supported (the '
+                                 "exchange of the heads' gradients is not built)")
+            if cfg.dcl_d_weight > 0:
+                raise ValueError('RickTrainer: subspace_freq > 0 together with dcl_d_weight > 0 is not supported (the contrastive '
+                                 'term needs the whole feature list, which a patch step that leaves the trunk early does not '
+                                 'have: not built)')
+            if cfg.n_anchors < 1 or not cfg.subspace_std >= 0 or not math.isfinite(cfg.subspace_std):
+                raise ValueError('RickTrainer: n_anchors must be >= 1 and subspace_std finite and >= 0')
+            if patch_heads is None:
+                patch_heads = patchd.PatchHeads().to(self.device)
+            n_taps = len(patchd.patch_taps(discriminator, patch_heads.channels))
+            if not 1 <= cfg.feat_ind <= min(n_taps, len(patch_heads.new_conv)):
+                raise ValueError(f'RickTrainer: feat_ind {cfg.feat_ind} with {n_taps} patch taps in the discriminator and '
+                                 f'{len(patch_heads.new_conv)} heads')
+            if next(patch_heads.parameters()).device != self.device:
+                raise ValueError(f'RickTrainer: patch_heads on {next(patch_heads.parameters()).device}, generator on {self.device}')
+        elif patch_heads is not None:
+            raise ValueError('RickTrainer: patch_heads given with subspace_freq = 0')
         # packed conv weights: one refresh launch per network
         self._pack_groups = [op.register_pack_group(net) for net in (generator, discriminator)]
         self._ema_pack_groups = [op.register_pack_group(net) for net in (g_ema, d_ema)]
@@ -425,6 +455,16 @@ class RickTrainer:
             self.svd_g, self.svd_d = self._adapters.values()
             for flat, optim in nets:
                 optim.set_mask(self._adapters[flat].frozen_mask(rest=cfg.svd_train_rest))
+        # CDC's patch-level discriminator and anchor sampling (rick_amd/patchd.py): the heads' parameters in a FlatParams of their
+        # own with a MaskedFlatAdam at D's learning rate and betas (the arrangement FlatAdapter has for its factors), stepped
+        # with D's optimiser on patch D steps only: no masks, no EMA copy, no part in the Fisher sweep.  `anchors` may be set.
+        self.patch_heads, self.anchors, self.last_patch = patch_heads, None, None
+        self.head_flat = self.head_optim = None
+        if cfg.subspace_freq > 0:
+            self._head_pack = op.register_pack_group(patch_heads)
+            self.head_flat = FlatParams(patch_heads.named_parameters())
+            self.head_optim = MaskedFlatAdam(self.head_flat, self.d_optim.lr, tuple(self.d_optim.betas))
+            self.anchors = torch.randn(cfg.n_anchors, cfg.latent, device=self.device)
         self.ewc = None
         if ewc is not None:
             self.set_ewc(*ewc) if isinstance(ewc, (tuple, list)) else self.set_ewc(ewc)
@@ -477,7 +517,8 @@ class RickTrainer:
         for n, p in self._d_all.items():
             p.requires_grad = (('final' in n) if warm else True) and d_optim_filter(n)
 
-    def _d_frozen(self):
+    def _d_frozen(self, extra=()):
+        """requires_grad off on every parameter of D (and of `extra`) inside the context."""
         class _Ctx:
             def __init__(s, params):
                 s.params, s.flags = params, None
@@ -490,7 +531,7 @@ class RickTrainer:
             def __exit__(s, *a):
                 for p, f in zip(s.params, s.flags):
                     p.requires_grad = f
-        return _Ctx(list(self._d_all.values()))
+        return _Ctx(list(self._d_all.values()) + list(extra))
 
     def _reduce(self, flat):
         if self.dp is not None:
@@ -784,16 +825,24 @@ class RickTrainer:
         self._ada_sum.zero_()
 
     # ---- steps (each returns the loss tensor; no host sync)
-    def d_step(self, real_img, noise, i=10 ** 9, g_noise=None, graph=False, dcl_layers=None, dcl_inject=None):
+    def d_step(self, real_img, noise, i=10 ** 9, g_noise=None, graph=False, dcl_layers=None, dcl_inject=None, patch=None):
         """Logistic D step.  With cfg.dcl_d_weight > 0 the discriminator contrastive term (rick_amd/dcl.py) is added before the one
         backward(): anchors and negatives are the two halves of the feature list the pass over cat(fake, real) returns anyway, the
         positives come from one no-grad pass G_s -> D_s with the mixing index and noise maps of the fakes (drawn here, handed to
         both generators).  Its drawn layers change the launch list, so such a step is never captured: `graph=True` then runs the
         eager path, as g_step does with the distance-consistency term.  `dcl_layers` and `dcl_inject` fix the draws (tests);
-        `g_noise` fixes the noise maps."""
+        `g_noise` fixes the noise maps.  With cfg.subspace_freq > 0 (rick_amd/patchd.py) the step also runs eagerly under
+        `graph=True`; `patch=p_ind` then sends cat(fake, real) through patchd.patch_logits at that tap instead of the whole
+        discriminator — the logistic loss over every entry of the two patch maps — and steps the heads' own Adam with D's; the
+        augmentation seam applies to the images as on image-level steps, ADA's controller is left alone.  Parameters behind
+        the exit get no gradient from autograd; their slices of the flat gradient stay zero and Adam (beta1 = 0) leaves them
+        bit for bit, as it does the heads of the other taps."""
         self._set_d_stage(i)
         dcl_on = self.cfg.dcl_d_weight > 0
-        if dcl_on and graph:
+        patch_on = self.cfg.subspace_freq > 0
+        if patch is not None and not patch_on:
+            raise ValueError('RickTrainer.d_step: patch= needs cfg.subspace_freq > 0')
+        if (dcl_on or patch_on) and graph:
             graph = False
             if noise is None:
                 noise = mixing_noise(real_img.shape[0], self.cfg.latent, self.cfg.mixing, self.device)
@@ -820,7 +869,12 @@ class RickTrainer:
             # one pass over cat(fake, real): identical to the reference's two calls (per-call minibatch-stddev
             # statistics are kept), half the launches and twice the GEMM rows per launch
             with self._sink():                   # conv weight gradients are added straight into the flat buffer
-                pred, feats = self.d(x, calls=2)
+                if patch is not None:
+                    from . import patchd
+                    pred = patchd.patch_logits(self.d, self.patch_heads, x, patch)
+                    self.head_flat.zero_grad()
+                else:
+                    pred, feats = self.d(x, calls=2)
                 fake_pred, real_pred = pred.chunk(2, 0)
                 d_loss = d_logistic_loss(real_pred, fake_pred)
                 total = d_loss
@@ -832,7 +886,7 @@ class RickTrainer:
                                                                   layers, self.cfg.dcl_tau)
                     total = d_loss + self.cfg.dcl_d_weight * dcl_loss
                     self.losses['dcl_d'] = dcl_loss.detach()
-                if self._ada_sum is not None:
+                if self._ada_sum is not None and patch is None:
                     self._ada_sum.add_(torch.sign(real_pred.detach()).sum())
                 self._zero_grad(self.d_flat)
                 # bias / noise-strength sums: one second-stage launch for the whole pass; (RICK_WGRAD_OVERLAP=1: sunk weight
@@ -850,7 +904,10 @@ class RickTrainer:
                 # the reference draws real's parameters first, then fake's; the launch runs over cat(fake, real)
                 aug.prepare('d', 2, batch, reverse=True)
         self._run(key, fb, self.d_flat, self.d_optim, pre=pre if (graph or aug) else None)
-        self._ada_after_d_step(batch)
+        if patch is not None:
+            self.head_optim.step()
+        else:
+            self._ada_after_d_step(batch)
         return self.losses['d']
 
     def r1_step(self, real_img, i=10 ** 9, graph=False):
@@ -948,15 +1005,21 @@ class RickTrainer:
             out['dcl_g'] = self._dcl_g_term(dcl_noise, dcl_layers, g_noise)
         return out
 
-    def g_step(self, noise, g_noise=None, graph=False, cdc_noise=None, cdc_layers=None, dcl_noise=None, dcl_layers=None):
+    def g_step(self, noise, g_noise=None, graph=False, cdc_noise=None, cdc_layers=None, dcl_noise=None, dcl_layers=None,
+               patch=None):
         """Non-saturating G step.  With cfg.cdc_weight > 0 the distance-consistency term is added before the one backward():
         its drawn layers change the launch list from step to step, so such a step is never captured — `graph=True` then runs
         the eager path (its own mixing noise, no step graph) while every other step type keeps replaying.  `cdc_noise`
         [cdc_batch, latent] and `cdc_layers` fix the term's draws (tests); `g_noise` also fixes its noise maps.  The generator
-        contrastive term (cfg.dcl_g_weight > 0, `dcl_noise` / `dcl_layers`) is treated the same way."""
+        contrastive term (cfg.dcl_g_weight > 0, `dcl_noise` / `dcl_layers`) is treated the same way, and so is every G step with
+        cfg.subspace_freq > 0 (rick_amd/patchd.py): `patch=p_ind` takes the non-saturating loss over the patch map of
+        patchd.patch_logits at that tap; neither the discriminator nor the heads get gradients."""
         cdc_on = self.cfg.cdc_weight > 0
         dcl_on = self.cfg.dcl_g_weight > 0
-        if (cdc_on or dcl_on) and graph:
+        patch_on = self.cfg.subspace_freq > 0
+        if patch is not None and not patch_on:
+            raise ValueError('RickTrainer.g_step: patch= needs cfg.subspace_freq > 0')
+        if (cdc_on or dcl_on or patch_on) and graph:
             graph = False
             if noise is None:
                 noise = mixing_noise(self.cfg.batch, self.cfg.latent, self.cfg.mixing, self.device)
@@ -974,11 +1037,15 @@ class RickTrainer:
         aug = self._augmenter
 
         def fb():
-            with self._sink(), self._d_frozen():
+            with self._sink(), self._d_frozen(self.patch_heads.parameters() if self.patch_heads is not None else ()):
                 fake = box.pop('fake')
                 if aug:                          # with gradients: the adjoint carries them back to G
                     fake = aug.apply(fake, aug.blocks['g'].dev)
-                fake_pred, _ = self.d(fake)
+                if patch is not None:
+                    from . import patchd
+                    fake_pred = patchd.patch_logits(self.d, self.patch_heads, fake, patch)
+                else:
+                    fake_pred, _ = self.d(fake)
                 g_loss = g_nonsaturating_loss(fake_pred)
                 total = g_loss
                 if cdc_on and not dcl_on:
@@ -1159,13 +1226,23 @@ class RickTrainer:
             real_img = self._real
         nz = (lambda b: None) if graph else (lambda b: mixing_noise(b, cfg.latent, cfg.mixing, self.device))
         self._mark('begin')
-        self.d_step(real_img, nz(cfg.batch), i, graph=graph)
+        nz_dg, patch = nz, {}                                 # the noise and the extra arguments of the D and the G step
+        if cfg.subspace_freq > 0:
+            # CDC's schedule (rick_amd/patchd.py): an anchor iteration draws the latents of both steps from the anchor subspace and
+            # keeps the image-level discriminator; the others use the patch path at one drawn tap in both steps
+            from . import patchd
+            which, p_ind = self.last_patch = patchd.draw_patch(i, cfg.subspace_freq, cfg.feat_ind)
+            if which == 0:
+                nz_dg = lambda b: [patchd.sample_anchor_latents(self.anchors, b, cfg.subspace_std)]     # noqa: E731
+            else:
+                patch = {'patch': p_ind}
+        self.d_step(real_img, nz_dg(cfg.batch), i, graph=graph, **patch)
         self._mark('d')
         if i % cfg.d_reg_every == 0:       # with augmentation: the D step's augmented reals (:463-466)
             self.r1_step(self._aug_real if cfg.augment else real_img, i, graph=graph)
             self._mark('r1')
         if i >= cfg.warmup_iter:
-            self.g_step(nz(cfg.batch), graph=graph)
+            self.g_step(nz_dg(cfg.batch), graph=graph, **patch)
             self._mark('g')
             if i % cfg.g_reg_every == 0:
                 self.plr_step(nz(max(1, cfg.batch // cfg.path_batch_shrink)), graph=graph)
