@@ -468,7 +468,8 @@ int rick_demod_bwd_w_f32(const float *w, const float *s, const float *d, const f
  *   bwd: grad[gw_off + c*K + k] = scale * sum_b gs[io_off + b*C + c] * lat[b, lat_idx, k];  grad[gb_off + c] = sum_b gs[..]
  * (gw_off / gb_off < 0: no weight / bias gradient; a layer with neither is skipped and its gs is not read;
  * accumulate != 0: the gradients are ADDED to what grad holds — grad + offsets then address the parameters' own
- * gradient buffers).  `descs_device` lives in device memory.  K % 256 == 0, B <= 8, grad 16-byte aligned. */
+ * gradient buffers).  `descs_device` lives in device memory.  K % 256 == 0, B <= 8, grad 16-byte aligned.  The forward
+ * stages the latent rows in LDS: B * K * 4 bytes > 64 KB is refused with RICK_EINVAL before anything is launched. */
 typedef struct {
     const float *w;         /* [C, K] */
     const float *b;         /* [C] or NULL */
@@ -511,7 +512,9 @@ int rick_demod_bwd_s_multi_f32(const float *s_flat, const float *d_flat, const f
 /* EqualLinear forward on a short batch (the mapping network, model_probe_tune.py:139-173, 418-428; no autograd):
  *   x' = pixelnorm ? x * rsqrt(mean_k x^2 + 1e-8) : x                                  (PixelNorm, :92-98)
  *   out[b,o] = act(scale * sum_k x'[b,k] W[o,k] + bias[o] * bias_mul);  act != 0: gain * leaky_relu(., slope)
- * x [B, K], W [O, K], bias [O] or NULL, out [B, O].  B <= 16, K % 4 == 0, x / W 16-byte aligned. */
+ * x [B, K], W [O, K], bias [O] or NULL, out [B, O].  B <= 16, K % 4 == 0, x / W 16-byte aligned.  x is staged in LDS:
+ * B * K * 4 bytes > 160 KB (the CU's LDS; the discriminator's [4, 8192] layer takes 128 KB) is refused with RICK_EINVAL
+ * before anything is launched. */
 int rick_equal_linear_f32(const float *x, const float *W, const float *bias, float *out, int B, int K, int O,
                           float scale, float bias_mul, int act, float slope, float gain, int pixelnorm, void *stream);
 /* EqualLinear WITH gradients on a short batch (the discriminator's final layers, model_probe_tune.py:699-702, in every D pass;

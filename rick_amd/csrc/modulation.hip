@@ -537,7 +537,9 @@ extern "C" int rick_modbank_blocks(int C) { return cdiv(C, MB_ROWS); }
 extern "C" int rick_modbank_fwd_f32(const float *lat, int B, int n_latent, int K, const rick_modbank_desc *descs_device, int n,
                                     int total_blocks, float scale, float *out, void *stream) {
     if (!lat || !descs_device || !out || B < 1 || B > MB_MAXB || K < 256 || (K & 255) || n < 1 || total_blocks < 1) return RICK_EINVAL;
-    hipLaunchKernelGGL(modbank_fwd_kernel, dim3((unsigned)total_blocks), dim3(256), (size_t)B * K * 4, (hipStream_t)stream, lat, B,
+    const size_t lds = (size_t)B * K * sizeof(float);
+    if (lds > 64 * 1024) return RICK_EINVAL;
+    hipLaunchKernelGGL(modbank_fwd_kernel, dim3((unsigned)total_blocks), dim3(256), lds, (hipStream_t)stream, lat, B,
                        n_latent, K, descs_device, n, scale, out);
     RICK_LAUNCH_STATUS();
 }
@@ -618,7 +620,12 @@ extern "C" int rick_equal_linear_f32(const float *x, const float *W, const float
                                      void *stream) {
     if (!x || !W || !out || B < 1 || B > EL_MAXB || K < 4 || (K & 3) || O < 1) return RICK_EINVAL;
     if (((uintptr_t)x | (uintptr_t)W) & 15) return RICK_EINVAL;
-    hipLaunchKernelGGL(equal_linear_kernel, dim3((unsigned)cdiv(O, 4 * EL_CPW)), dim3(256), (size_t)B * K * 4, (hipStream_t)stream,
+    // x [B][K] in LDS: EqualLinear.forward sends the discriminator's first final layer here in a no-grad pass of up to 5 images
+    // ([4, 8192]: 128 KB), so the limit is the CU's 160 KB, not the 64 KB a kernel gets by default
+    const size_t lds = (size_t)B * K * sizeof(float);
+    if (lds > 160 * 1024) return RICK_EINVAL;
+    if (lds > 64 * 1024) RICK_LDS160_ONCE(equal_linear_kernel);
+    hipLaunchKernelGGL(equal_linear_kernel, dim3((unsigned)cdiv(O, 4 * EL_CPW)), dim3(256), lds, (hipStream_t)stream,
                        x, W, bias, out, B, K, O, scale, bias_mul, act, slope, gain, pixelnorm);
     RICK_LAUNCH_STATUS();
 }
