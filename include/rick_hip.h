@@ -711,6 +711,46 @@ int rick_fc_f32(const float *x, const float *wpk, const float *bias, float *ws, 
                 void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * CLIP — the ViT image tower of CLIP (Radford et al., 2021; rick_amd/clip.py), forward only: unnormalised image embeddings
+ * as `encode_image` returns them, for FID / KID in CLIP space and as the first step of the CLIP-guided adaptation recipes.
+ * Activations are fp32 rows [N * T][Wd] (T = G^2 + 1 tokens per image).
+ * rick_clip_input_f32: planar x [N, 3, H, W] in [-1, 1] -> out [N, S, S, 4] (channel 3 = 0): F.interpolate(mode='bicubic',
+ *   align_corners=False) to S x S (source s = (float(in) / float(S)) * (dst + 0.5) - 0.5, taps floor(s) - 1 .. floor(s) + 2
+ *   with indices clamped at the border, cubic convolution weights with A = -0.75, no antialiasing, overshoot kept; the four
+ *   taps of a row summed in order, then the four rows), then v = (x * 0.5 + 0.5 - mean_c) / std_c as four correctly rounded
+ *   fp32 operations, mean = (0.48145466, 0.4578275, 0.40821073), std = (0.26862954, 0.26130258, 0.27577711).  At H == W == S
+ *   the weights are exactly (0, 1, 0, 0): finite values are copied bit for bit before the affine.
+ * rick_inc_conv_lin_f32: rick_inc_conv_f32's GEMM (same operands, same tiles, exact fp32 products, no split-K) with the
+ *   linear epilogue v = acc + bias[col]; v = act(v), act = 0 the identity, 1 QuickGELU; v += res[m, col] if res != NULL.
+ *   One destination: nseg = 1, written at dst[0] + m * ldc[0] + c0[0] + col; res is indexed like dst[0] and may be dst[0]
+ *   itself (the in-place residual: every element is read and written by one thread).  QuickGELU in fp32, every operation
+ *   rounded on its own: u * (1 / (1 + expf(-(1.702f * u)))).  A row's result does not depend on the other rows.  A linear
+ *   layer on rows [M, K] is the 1 x 1 convolution of N = M images of 1 x 1 x K.
+ * rick_clip_tokens_f32: patches [N, T - 1, C] (the patch GEMM's output, row-major patches), cls [C], pos [T, C] ->
+ *   out [N, T, C] = LayerNorm([cls ; patches] + pos) with ln_pre's w, b [C].
+ * rick_clip_layernorm_f32: rows in[r * ldx + c], r < R, c < C (ldx >= C: ln_post reads token 0 of every image with
+ *   ldx = T * C) -> out [R, C] compact.  C % 4 == 0, C <= 2048, ldx % 4 == 0.
+ *   Both: one wave per row, the row held in registers, lane l owning columns 4 l + 256 j.  Pass 1: the lane adds its columns
+ *   in ascending order, then the 32, 16, ..., 1 xor butterfly; mean = sum / C.  Pass 2: the same order over fmaf(d, d, .),
+ *   d = x - mean; var = sum / C (biased).  y = fmaf(d * (1 / sqrtf(var + eps)), w, b).
+ * rick_clip_attention_f32: qkv [N, T, 3 Wd] (columns q | k | v, head h owning [h D, (h + 1) D) of each), Wd = heads * D,
+ *   D in {16, 32, 64}, T <= 257 -> out [N, T, Wd] = softmax(q k^T / sqrt(D)) v per head.  One block per (image, head) with K
+ *   and V of the head in LDS (up to 137 KB).  score[k] = (fmaf chain over c ascending) * (1 / sqrt(D)) in fp32; the row
+ *   maximum is subtracted, e = expf, the denominator is the sum per lane over its keys l + 64 j ascending, then the xor
+ *   butterfly; p = e / den; out[c] = fmaf chain of p[k] v[k][c] over k ascending.  A query row's result depends on its own
+ *   image and head only.
+ * The projection runs on rick_fc_f32.  Unsupported shapes return 22.
+ * No atomics: every output element has one writer and a fixed summation order (bit-identical from run to run). */
+int rick_clip_input_f32(const float *x, float *out, int N, int H, int W, int S, void *stream);
+int rick_inc_conv_lin_f32(const float *in, const float *wpk, const float *bias, const float *res, int act,
+                          const rick_inc_conv *a, void *stream);
+int rick_clip_tokens_f32(const float *patches, const float *cls, const float *pos, const float *w, const float *b, float *out,
+                         int N, int T, int C, float eps, void *stream);
+int rick_clip_layernorm_f32(const float *in, int64_t ldx, const float *w, const float *b, float *out, int R, int C, float eps,
+                            void *stream);
+int rick_clip_attention_f32(const float *qkv, float *out, int N, int T, int heads, int D, void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * Gram — the Gram matrix of a few very long rows and its adjoint (rick_amd/cdc.py): the device side of the cross-domain
  * distance-consistency loss, which needs the cosine similarity of whole generator feature maps between batch members.
  * x is B rows (1 <= B <= 8) of n >= 1 fp32 values, row stride n, 64-bit indices.  A row is an unordered bag of values: any

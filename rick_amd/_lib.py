@@ -233,6 +233,11 @@ SIGNATURES = {
     'rick_patch_head_fwd_f32': (c_int, [c_fp] * 4 + [c_int] * 4 + [c_f] * 3 + [c_fp]),
     'rick_patch_head_bwd_f32': (c_int, [c_fp] * 6 + [c_int] * 4 + [c_f] * 3 + [c_fp]),
     'rick_patch_head_bwd_finish_f32': (c_int, [c_fp] * 3 + [c_int] * 4 + [c_f, c_fp]),
+    'rick_clip_input_f32': (c_int, [c_fp, c_fp, c_int, c_int, c_int, c_int, c_fp]),
+    'rick_inc_conv_lin_f32': (c_int, [c_fp, c_fp, c_fp, c_fp, c_int, ctypes.POINTER(IncConv), c_fp]),
+    'rick_clip_tokens_f32': (c_int, [c_fp] * 6 + [c_int] * 3 + [c_f, c_fp]),
+    'rick_clip_layernorm_f32': (c_int, [c_fp, c_i64, c_fp, c_fp, c_fp, c_int, c_int, c_f, c_fp]),
+    'rick_clip_attention_f32': (c_int, [c_fp, c_fp, c_int, c_int, c_int, c_int, c_fp]),
 }
 
 if not os.path.exists(LIB_PATH):

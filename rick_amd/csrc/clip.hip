@@ -1,0 +1,289 @@
+// CLIP ViT image tower (Radford et al., 2021), forward only — include/rick_hip.h "CLIP".
+//
+// The five GEMMs of a layer run on rick_inc_conv_lin_f32 (inception.hip).  This file holds what a transformer needs around
+// them: the bicubic input, token assembly fused with ln_pre, LayerNorm and multi-head attention.  Activations are fp32 rows
+// [tokens][width].  Every output element is written by exactly one thread with a fixed summation order: no atomics, run-to-run
+// bit-identical, and an image's values do not depend on the other images of the call.
+#include "common.h"
+
+#define CL_MAXJ 8              // a row of up to 2048 columns in registers: lane l holds columns 4 l + 256 j, j < 8
+#define CL_MAXC (256 * CL_MAXJ)
+#define CL_MAXT 257            // ViT-L/14 at 224
+#define CL_KEYS ((CL_MAXT + 63) / 64)
+
+// ---- input: bicubic resize (F.interpolate, mode='bicubic', align_corners=False, no antialias) + CLIP's affine, NCHW -> NHWC4 --
+// ATen's cubic convolution, A = -0.75: weights of the taps floor(s) - 1 .. floor(s) + 2 at t = s - floor(s).  At t = 0 they
+// are exactly (0, 1, 0, 0) in these forms, with or without contraction into FMAs.
+__device__ __forceinline__ float cl_cubic1(float x) { return ((-0.75f + 2.f) * x - (-0.75f + 3.f)) * x * x + 1.f; }
+__device__ __forceinline__ float cl_cubic2(float x) { return ((-0.75f * x - 5.f * -0.75f) * x + 8.f * -0.75f) * x - 4.f * -0.75f; }
+__device__ __forceinline__ void cl_cubic_taps(int dst, float scale, int n_in, int idx[4], float w[4]) {
+    const float s = __fsub_rn(__fmul_rn(scale, (float)dst + 0.5f), 0.5f);     // area_pixel_compute_source_index, cubic: no clamp at 0
+    const float fl = floorf(s), t = s - fl;
+    const int i0 = (int)fl;
+    w[0] = cl_cubic2(t + 1.f);
+    w[1] = cl_cubic1(t);
+    w[2] = cl_cubic1(1.f - t);
+    w[3] = cl_cubic2(2.f - t);
+#pragma unroll
+    for (int k = 0; k < 4; k++) idx[k] = min(max(i0 - 1 + k, 0), n_in - 1);   // border: clamped source indices
+}
+
+__global__ __launch_bounds__(256) void clip_input_kernel(const float *__restrict__ x, float *__restrict__ out, int N, int H, int W,
+                                                         int S, float sh, float sw) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (int64_t)N * S * S) return;
+    const int ox = (int)(i % S), oy = (int)((i / S) % S), n = (int)(i / ((int64_t)S * S));
+    int iy[4], ix[4];
+    float wy[4], wx[4];
+    cl_cubic_taps(oy, sh, H, iy, wy);
+    cl_cubic_taps(ox, sw, W, ix, wx);
+    const float mean[3] = {0.48145466f, 0.4578275f, 0.40821073f}, std[3] = {0.26862954f, 0.26130258f, 0.27577711f};
+    float r[3];
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        const float *p = x + ((int64_t)n * 3 + c) * H * W;
+        float v = 0.f;
+#pragma unroll
+        for (int a = 0; a < 4; a++) {                         // rows in tap order; within a row the four taps in order
+            const float *q = p + (int64_t)iy[a] * W;
+            float row = wx[0] * q[ix[0]];
+#pragma unroll
+            for (int b = 1; b < 4; b++) row = fmaf(wx[b], q[ix[b]], row);
+            v = a == 0 ? wy[0] * row : fmaf(wy[a], row, v);
+        }
+        // (v * 0.5 + 0.5 - mean) / std: four correctly rounded fp32 operations, as torch evaluates the expression
+        r[c] = __fdiv_rn(__fsub_rn(__fadd_rn(__fmul_rn(v, 0.5f), 0.5f), mean[c]), std[c]);
+    }
+    reinterpret_cast<float4 *>(out)[i] = make_float4(r[0], r[1], r[2], 0.f);
+}
+
+// ---- LayerNorm of one row held in registers ---------------------------------------------------------------------------------
+// Lane l owns columns 4 l + 256 j.  Pass 1: the lane adds its columns in ascending order, wave_sum (xor butterfly 32 .. 1),
+// mean = sum / C.  Pass 2: the lane adds fmaf(d, d, .) of d = x - mean in the same order, wave_sum, var = sum / C (biased).
+// y = fmaf(d * rstd, w, b), rstd = 1 / sqrtf(var + eps).  Never E[x^2] - mean^2.
+__device__ __forceinline__ void cl_layernorm_row(const float4 (&x)[CL_MAXJ], int C, int lane, const float *__restrict__ w,
+                                                 const float *__restrict__ b, float eps, float *__restrict__ out) {
+    float s = 0.f;
+#pragma unroll
+    for (int j = 0; j < CL_MAXJ; j++)
+        if (4 * lane + 256 * j < C) {
+            s += x[j].x;
+            s += x[j].y;
+            s += x[j].z;
+            s += x[j].w;
+        }
+    const float mean = wave_sum(s) / (float)C;
+    float q = 0.f;
+#pragma unroll
+    for (int j = 0; j < CL_MAXJ; j++)
+        if (4 * lane + 256 * j < C) {
+            const float dx = x[j].x - mean, dy = x[j].y - mean, dz = x[j].z - mean, dw = x[j].w - mean;
+            q = fmaf(dx, dx, q);
+            q = fmaf(dy, dy, q);
+            q = fmaf(dz, dz, q);
+            q = fmaf(dw, dw, q);
+        }
+    const float rstd = 1.f / sqrtf(wave_sum(q) / (float)C + eps);
+#pragma unroll
+    for (int j = 0; j < CL_MAXJ; j++) {
+        const int c = 4 * lane + 256 * j;
+        if (c < C) {
+            const float4 wv = *reinterpret_cast<const float4 *>(w + c), bv = *reinterpret_cast<const float4 *>(b + c);
+            float4 y;
+            y.x = fmaf((x[j].x - mean) * rstd, wv.x, bv.x);
+            y.y = fmaf((x[j].y - mean) * rstd, wv.y, bv.y);
+            y.z = fmaf((x[j].z - mean) * rstd, wv.z, bv.z);
+            y.w = fmaf((x[j].w - mean) * rstd, wv.w, bv.w);
+            *reinterpret_cast<float4 *>(out + c) = y;
+        }
+    }
+}
+
+// rows [R, C] with a row stride ldx -> out [R, C] compact.  One wave per row, four rows per block.
+__global__ __launch_bounds__(256) void clip_layernorm_kernel(const float *__restrict__ in, int64_t ldx, const float *__restrict__ w,
+                                                             const float *__restrict__ b, float *__restrict__ out, int R, int C,
+                                                             float eps) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (row >= R) return;                                     // wave-uniform
+    const float *p = in + (int64_t)row * ldx;
+    float4 x[CL_MAXJ];
+#pragma unroll
+    for (int j = 0; j < CL_MAXJ; j++) {
+        const int c = 4 * lane + 256 * j;
+        x[j] = c < C ? *reinterpret_cast<const float4 *>(p + c) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    cl_layernorm_row(x, C, lane, w, b, eps, out + (int64_t)row * C);
+}
+
+// tokens [N, T, C] = ln_pre([class_embedding ; patches [N, T - 1, C]] + positional_embedding [T, C]): one wave per token
+__global__ __launch_bounds__(256) void clip_tokens_kernel(const float *__restrict__ patches, const float *__restrict__ cls,
+                                                          const float *__restrict__ pos, const float *__restrict__ w,
+                                                          const float *__restrict__ b, float *__restrict__ out, int N, int T, int C,
+                                                          float eps) {
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (row >= (int64_t)N * T) return;                        // wave-uniform
+    const int t = (int)(row % T);
+    const int64_t n = row / T;
+    const float *p = t == 0 ? cls : patches + (n * (T - 1) + (t - 1)) * C;
+    const float *e = pos + (int64_t)t * C;
+    float4 x[CL_MAXJ];
+#pragma unroll
+    for (int j = 0; j < CL_MAXJ; j++) {
+        const int c = 4 * lane + 256 * j;
+        x[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (c < C) {
+            const float4 a = *reinterpret_cast<const float4 *>(p + c), d = *reinterpret_cast<const float4 *>(e + c);
+            x[j] = make_float4(a.x + d.x, a.y + d.y, a.z + d.z, a.w + d.w);
+        }
+    }
+    cl_layernorm_row(x, C, lane, w, b, eps, out + row * C);
+}
+
+// ---- attention ----------------------------------------------------------------------------------------------------------------
+// One block per (image, head); K [T][D + 1] (the odd stride spreads the lanes' key rows over the banks) and V [T][D] of that
+// head are staged once in LDS.  Wave w takes the query rows w, w + 4, ...:
+//   score[k] = (sum_c q[c] K[k][c], one fmaf chain over c ascending from 0) * (1 / sqrt(D)), lane l owning keys l + 64 j;
+//   m = max (per lane over j, then the xor butterfly); e[k] = expf(score[k] - m);
+//   den = per lane e over j ascending, then wave_sum; p[k] = e[k] / den (F.softmax's form), through LDS to every lane;
+//   out[c] = sum_k p[k] V[k][c], one fmaf chain over k ascending from 0, lane c < D.
+// The two barriers per row are taken by all four waves (the row loop has one trip count for the block).
+__device__ __forceinline__ float cl_wave_max(float v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
+    return v;
+}
+
+static size_t cl_attention_lds(int T, int D) { return sizeof(float) * ((size_t)T * D + (size_t)T * (D + 1) + 4 * (size_t)((T + 3) & ~3)); }
+
+template <int D>
+__global__ __launch_bounds__(256) void clip_attention_kernel(const float *__restrict__ qkv, float *__restrict__ out, int T, int Wd,
+                                                             int heads) {
+    extern __shared__ __attribute__((aligned(16))) float cl_lds[];
+    constexpr int KS = D + 1;
+    constexpr float scale = D == 16 ? 0.25f : D == 64 ? 0.125f : 0.17677669529663687f;      // 1 / sqrt(D)
+    const int Tp = (T + 3) & ~3;
+    float *Vs = cl_lds, *Ks = Vs + T * D, *Ps = Ks + T * KS;
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const int n = blockIdx.x / heads, h = blockIdx.x % heads;
+    const int64_t ld = 3 * (int64_t)Wd;
+    const float *base = qkv + (int64_t)n * T * ld + h * D;
+    for (int i = t; i < T * (D / 4); i += 256) {
+        const int k = i / (D / 4), c = 4 * (i % (D / 4));
+        const float4 kv = *reinterpret_cast<const float4 *>(base + k * ld + Wd + c);
+        const float4 vv = *reinterpret_cast<const float4 *>(base + k * ld + 2 * Wd + c);
+        Ks[k * KS + c] = kv.x;
+        Ks[k * KS + c + 1] = kv.y;
+        Ks[k * KS + c + 2] = kv.z;
+        Ks[k * KS + c + 3] = kv.w;
+        *reinterpret_cast<float4 *>(Vs + k * D + c) = vv;
+    }
+    __syncthreads();
+    float *pw = Ps + w * Tp;
+    for (int r0 = 0; r0 < T; r0 += 4) {
+        const int row = r0 + w;
+        const bool ok = row < T;                              // wave-uniform
+        if (ok) {
+            float4 q[D / 4];
+#pragma unroll
+            for (int c = 0; c < D / 4; c++) q[c] = *reinterpret_cast<const float4 *>(base + row * ld + 4 * c);
+            float s[CL_KEYS], mx = -INFINITY;
+#pragma unroll
+            for (int j = 0; j < CL_KEYS; j++) {
+                const int k = lane + 64 * j;
+                s[j] = -INFINITY;
+                if (k < T) {
+                    const float *kr = Ks + k * KS;
+                    float a = 0.f;
+#pragma unroll
+                    for (int c = 0; c < D / 4; c++) {
+                        a = fmaf(q[c].x, kr[4 * c], a);
+                        a = fmaf(q[c].y, kr[4 * c + 1], a);
+                        a = fmaf(q[c].z, kr[4 * c + 2], a);
+                        a = fmaf(q[c].w, kr[4 * c + 3], a);
+                    }
+                    s[j] = a * scale;
+                }
+                mx = fmaxf(mx, s[j]);
+            }
+            mx = cl_wave_max(mx);
+            float den = 0.f;
+#pragma unroll
+            for (int j = 0; j < CL_KEYS; j++) {
+                s[j] = lane + 64 * j < T ? expf(s[j] - mx) : 0.f;
+                den += s[j];
+            }
+            den = wave_sum(den);
+#pragma unroll
+            for (int j = 0; j < CL_KEYS; j++)
+                if (lane + 64 * j < T) pw[lane + 64 * j] = s[j] / den;
+        }
+        __syncthreads();
+        if (ok && lane < D) {
+            float o = 0.f;
+            for (int k = 0; k < T; k++) o = fmaf(pw[k], Vs[k * D + lane], o);
+            out[((int64_t)n * T + row) * Wd + h * D + lane] = o;
+        }
+        __syncthreads();
+    }
+}
+
+// The 160 KB limit is raised once per kernel variant and device: the flags of RICK_LDS160_ONCE belong to its expansion site,
+// and this function template is one expansion site per D.
+template <int D>
+static void cl_attention_launch(const float *qkv, float *out, int N, int T, int Wd, int heads, hipStream_t st) {
+    const size_t lds = cl_attention_lds(T, D);
+    if (lds > 64 * 1024) RICK_LDS160_ONCE(clip_attention_kernel<D>);
+    hipLaunchKernelGGL(clip_attention_kernel<D>, dim3((unsigned)(N * heads)), dim3(256), lds, st, qkv, out, T, Wd, heads);
+}
+
+// ---- entries ------------------------------------------------------------------------------------------------------------------
+static bool cl_aligned16(const void *a, const void *b = nullptr, const void *c = nullptr, const void *d = nullptr) {
+    return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)d) % 16) == 0;
+}
+
+extern "C" int rick_clip_input_f32(const float *x, float *out, int N, int H, int W, int S, void *stream) {
+    if (!x || !out || N < 0 || H <= 0 || W <= 0 || S <= 0 || !cl_aligned16(out)) return RICK_EINVAL;
+    if ((int64_t)H * W > 0x7fffffff / 4 || (int64_t)N * S * S > ((int64_t)1 << 36)) return RICK_EINVAL;
+    if (N == 0) return 0;
+    hipLaunchKernelGGL(clip_input_kernel, dim3((unsigned)cdiv64((int64_t)N * S * S, 256)), dim3(256), 0, (hipStream_t)stream, x, out,
+                       N, H, W, S, (float)H / (float)S, (float)W / (float)S);
+    RICK_LAUNCH_STATUS();
+}
+
+extern "C" int rick_clip_layernorm_f32(const float *in, int64_t ldx, const float *w, const float *b, float *out, int R, int C,
+                                       float eps, void *stream) {
+    if (!in || !w || !b || !out || R < 0 || C <= 0 || (C & 3) || C > CL_MAXC || ldx < C || (ldx & 3) || !(eps >= 0.f) ||
+        !cl_aligned16(in, w, b, out))
+        return RICK_EINVAL;
+    if (R == 0) return 0;
+    hipLaunchKernelGGL(clip_layernorm_kernel, dim3((unsigned)cdiv(R, 4)), dim3(256), 0, (hipStream_t)stream, in, ldx, w, b, out, R, C,
+                       eps);
+    RICK_LAUNCH_STATUS();
+}
+
+extern "C" int rick_clip_tokens_f32(const float *patches, const float *cls, const float *pos, const float *w, const float *b,
+                                    float *out, int N, int T, int C, float eps, void *stream) {
+    if (!patches || !cls || !pos || !w || !b || !out || N < 0 || T < 2 || T > CL_MAXT || C <= 0 || (C & 3) || C > CL_MAXC ||
+        !(eps >= 0.f) || !cl_aligned16(patches, cls, pos, w) || !cl_aligned16(b, out))
+        return RICK_EINVAL;
+    if (N == 0) return 0;
+    if ((int64_t)N * T > 0x7fffffff) return RICK_EINVAL;
+    hipLaunchKernelGGL(clip_tokens_kernel, dim3((unsigned)cdiv64((int64_t)N * T, 4)), dim3(256), 0, (hipStream_t)stream, patches, cls,
+                       pos, w, b, out, N, T, C, eps);
+    RICK_LAUNCH_STATUS();
+}
+
+extern "C" int rick_clip_attention_f32(const float *qkv, float *out, int N, int T, int heads, int D, void *stream) {
+    if (!qkv || !out || N < 0 || T < 1 || T > CL_MAXT || heads < 1 || heads > 1024 || (D != 16 && D != 32 && D != 64) ||
+        !cl_aligned16(qkv, out))
+        return RICK_EINVAL;
+    if (N == 0) return 0;
+    if ((int64_t)N * heads > 0x7fffffff || cl_attention_lds(T, D) > 160 * 1024) return RICK_EINVAL;
+    const int Wd = heads * D;
+    hipStream_t st = (hipStream_t)stream;
+    if (D == 16) cl_attention_launch<16>(qkv, out, N, T, Wd, heads, st);
+    else if (D == 32) cl_attention_launch<32>(qkv, out, N, T, Wd, heads, st);
+    else cl_attention_launch<64>(qkv, out, N, T, Wd, heads, st);
+    RICK_LAUNCH_STATUS();
+}

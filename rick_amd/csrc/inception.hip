@@ -66,7 +66,13 @@ __device__ __forceinline__ float4 inc_ld_b(const float *wpk, int k0, int idx, in
 }
 // BWD = true is the data gradient of a 3x3 stride-1 pad-1 convolution (rick_inc_conv_bwd_f32): the same GEMM over the
 // transposed, rotated filter with the epilogue out = (mask > 0) ? acc + add : 0 in place of bias + ReLU; one destination.
-template <int NT, bool BWD = false>
+// LIN != 0 is the linear epilogue (rick_inc_conv_lin_f32): out = act(acc + bias) [+ res], act the identity (LIN = 1) or
+// QuickGELU (LIN = 2), res (the `add` argument) laid out like the one destination and possibly the destination itself.
+// QuickGELU in fp32, each operation rounded on its own: u * (1 / (1 + expf(-(1.702f * u)))).
+__device__ __forceinline__ float inc_quickgelu(float u) {
+    return __fmul_rn(u, __fdiv_rn(1.f, __fadd_rn(1.f, expf(-__fmul_rn(1.702f, u)))));
+}
+template <int NT, bool BWD = false, int LIN = 0>
 __global__ __launch_bounds__(256) void inc_conv_kernel(const float *__restrict__ in, const float *__restrict__ wpk,
                                                        const float *__restrict__ bias, rick_inc_conv a,
                                                        const float *__restrict__ mask, const float *__restrict__ add) {
@@ -162,6 +168,26 @@ __global__ __launch_bounds__(256) void inc_conv_kernel(const float *__restrict__
                     if (add) v += add[o];
                     if (mask) v = mask[o] > 0.f ? v : 0.f;
                     a.dst[0][o] = v;
+                }
+            continue;
+        }
+        if constexpr (LIN != 0) {
+            float *dst = a.dst[0] + a.c0[0] + col;
+            // the in-place residual is read through the destination pointer: `add` is __restrict__
+            const float *res = add == a.dst[0] ? a.dst[0] : add;
+            if (res) res += a.c0[0] + col;
+            const float b = bias[col];
+#pragma unroll
+            for (int i = 0; i < 2; i++)
+#pragma unroll
+                for (int e = 0; e < 16; e++) {
+                    const int m = m0 + wm * 64 + 32 * i + (e & 3) + 8 * (e >> 2) + 4 * h;
+                    if (m >= M) continue;
+                    const int64_t o = (int64_t)m * a.ldc[0];
+                    float v = acc[i][j][e] + b;
+                    if (LIN == 2) v = inc_quickgelu(v);
+                    if (res) v += res[o];
+                    dst[o] = v;
                 }
             continue;
         }
@@ -383,6 +409,35 @@ extern "C" int rick_inc_conv_bwd_f32(const float *gout, const float *wt, const f
         hipLaunchKernelGGL((inc_conv_kernel<2, true>), grid, dim3(256), 0, (hipStream_t)stream, gout, wt, nullptr, g, mask, add);
     else
         hipLaunchKernelGGL((inc_conv_kernel<1, true>), grid, dim3(256), 0, (hipStream_t)stream, gout, wt, nullptr, g, mask, add);
+    RICK_LAUNCH_STATUS();
+}
+
+extern "C" int rick_inc_conv_lin_f32(const float *in, const float *wpk, const float *bias, const float *res, int act,
+                                     const rick_inc_conv *a, void *stream) {
+    if (!in || !wpk || !bias || !a || (act != 0 && act != 1)) return RICK_EINVAL;
+    const rick_inc_conv g = *a;
+    if (g.N < 0 || g.IH <= 0 || g.IW <= 0 || g.Ci <= 0 || (g.Ci & 3) || g.KH <= 0 || g.KW <= 0 || g.SH <= 0 || g.SW <= 0 ||
+        g.PH < 0 || g.PW < 0 || g.Co <= 0 || g.nseg != 1 || (g.bn != 64 && g.bn != 128) || g.Cop % g.bn || g.Cop < g.Co)
+        return RICK_EINVAL;
+    if (g.OH != (g.IH + 2 * g.PH - g.KH) / g.SH + 1 || g.OW != (g.IW + 2 * g.PW - g.KW) / g.SW + 1 || g.OH <= 0 || g.OW <= 0)
+        return RICK_EINVAL;
+    if (((uintptr_t)in | (uintptr_t)wpk) % 16) return RICK_EINVAL;
+    if (g.seg_start[0] != 0 || g.seg_start[1] < g.Co || g.seg_start[2] < g.Co || g.seg_start[3] < g.Co || !g.dst[0] ||
+        g.c0[0] < 0 || g.c0[0] + g.Co > g.ldc[0])
+        return RICK_EINVAL;
+    if (g.N == 0) return 0;
+    const int64_t M = (int64_t)g.N * g.OH * g.OW;
+    if (M > 0x7fffffff || (int64_t)g.N * g.IH * g.IW * g.Ci > ((int64_t)1 << 40)) return RICK_EINVAL;
+    const dim3 grid((unsigned)cdiv64(M, IC_BM), (unsigned)(g.Cop / g.bn));
+    hipStream_t st = (hipStream_t)stream;
+    if (g.bn == 128 && act)
+        hipLaunchKernelGGL((inc_conv_kernel<2, false, 2>), grid, dim3(256), 0, st, in, wpk, bias, g, nullptr, res);
+    else if (g.bn == 128)
+        hipLaunchKernelGGL((inc_conv_kernel<2, false, 1>), grid, dim3(256), 0, st, in, wpk, bias, g, nullptr, res);
+    else if (act)
+        hipLaunchKernelGGL((inc_conv_kernel<1, false, 2>), grid, dim3(256), 0, st, in, wpk, bias, g, nullptr, res);
+    else
+        hipLaunchKernelGGL((inc_conv_kernel<1, false, 1>), grid, dim3(256), 0, st, in, wpk, bias, g, nullptr, res);
     RICK_LAUNCH_STATUS();
 }
 

@@ -169,6 +169,16 @@ def kid_from_features(codes_g, codes_r, n_subsets=100, subset_size=1000, degree=
     return mmds.mean(), mmds.std(unbiased=False), mmds
 
 
+def clip_similarity(fa, fb):
+    """Cosine similarities of two sets of embeddings, fa [na, D] and fb [nb, D] -> [na, nb] in fp64 on fa's device: the quantity
+    image-guided StyleGAN-NADA and "similarity to the few-shot targets" both start from (rick_amd/clip.py returns the
+    unnormalised embeddings)."""
+    if fa.dim() != 2 or fb.dim() != 2 or fa.shape[1] != fb.shape[1]:
+        raise RuntimeError(f'clip_similarity: expected [na, D] and [nb, D], got {tuple(fa.shape)} and {tuple(fb.shape)}')
+    a, b = fa.double(), fb.double().to(fa.device)
+    return (a / a.norm(dim=1, keepdim=True)) @ (b / b.norm(dim=1, keepdim=True)).T
+
+
 @torch.no_grad()
 def precision_recall_from_features(feats_real, feats_fake, k=3, block=4096):
     """Improved precision / recall (gan_metrics/precision_recall.py:50-66, 185-246) on the device.

@@ -1,0 +1,127 @@
+"""CLIP image embeddings (rick_amd/clip.py) on the GPU: synthetic ViT-B/32 weights (width 768, 12 layers, 12 heads, MLP 3072,
+patch 32, 224^2, projection 512) at n = 25 and n = 100 from 256^2 inputs.  Reports images/s, the device time of every kernel
+family (each family's launches of one forward pass, timed alone on the network's own buffers), and in the same run the same
+computation as an fp32 torch composition on the GPU (rick_amd.clip.torch_forward, the module's CPU-path code, on device
+tensors).  Seeded synthetic weights (timing only).
+
+  python tools/bench_clip.py [--iters 20] [--rounds 5]
+The two implementations are timed alternately, `--rounds` times each after a warm-up of both; the report gives the median
+and every round.  Prints a readable report and one JSON line."""
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+VIT_B32 = dict(width=768, patch=32, image=224, layers=12, mlp=3072, dim=512)
+
+
+def timed(fn, iters):
+    fn()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(iters):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / 1e3 / iters
+
+
+def families(net, n, x):
+    """{family: a function that issues that family's launches of one forward pass of n images}, on the plan's buffers."""
+    from rick_amd import _lib as L
+    from rick_amd.clip import EPS
+    from rick_amd.fc import run_fc
+    plan, c, lib = net._plan, net.cfg, L.lib
+    d, v, rows = plan._descriptors(n), plan.vec, n * c.tokens
+    out = torch.empty(n, c.dim, device=x.device)
+
+    def gemm(name, src, res=None, act=0):
+        wpk, bias, _, _ = plan.gemm[name]
+        L.check(lib.rick_inc_conv_lin_f32(src.data_ptr(), wpk.data_ptr(), bias.data_ptr(), None if res is None else res.data_ptr(), act,
+                                          d[name], L.stream_ptr()), 'rick_inc_conv_lin_f32')
+
+    def layernorm(name, src, ldx, dst, r):
+        L.check(lib.rick_clip_layernorm_f32(src.data_ptr(), ldx, v[name + '.w'].data_ptr(), v[name + '.b'].data_ptr(), dst.data_ptr(), r,
+                                            c.width, EPS, L.stream_ptr()), 'rick_clip_layernorm_f32')
+
+    def each_layer(fn):
+        return lambda: [fn(f'blocks.{i}.') for i in range(c.layers)]
+
+    def layernorms():
+        for i in range(c.layers):
+            layernorm(f'blocks.{i}.ln1', plan.tok, c.width, plan.ln, rows)
+            layernorm(f'blocks.{i}.ln2', plan.tok, c.width, plan.ln, rows)
+        layernorm('ln_post', plan.tok, c.tokens * c.width, plan.post, n)
+
+    return {
+        'input (bicubic + affine)': lambda: L.check(lib.rick_clip_input_f32(x.data_ptr(), plan.x0.data_ptr(), n, x.shape[2], x.shape[3],
+                                                                            c.size, L.stream_ptr()), 'rick_clip_input_f32'),
+        'patch embedding GEMM': lambda: gemm('patch', plan.x0),
+        'tokens + ln_pre': lambda: L.check(lib.rick_clip_tokens_f32(plan.patches.data_ptr(), v['cls'].data_ptr(), v['pos'].data_ptr(),
+                                                                    v['ln_pre.w'].data_ptr(), v['ln_pre.b'].data_ptr(), plan.tok.data_ptr(),
+                                                                    n, c.tokens, c.width, EPS, L.stream_ptr()), 'rick_clip_tokens_f32'),
+        'LayerNorm (2 per layer + ln_post)': layernorms,
+        'q/k/v GEMM': each_layer(lambda b: gemm(b + 'qkv', plan.ln)),
+        'attention': each_layer(lambda b: L.check(lib.rick_clip_attention_f32(plan.qkv.data_ptr(), plan.att.data_ptr(), n, c.tokens, c.heads,
+                                                                              c.width // c.heads, L.stream_ptr()), 'rick_clip_attention_f32')),
+        'out_proj GEMM + residual': each_layer(lambda b: gemm(b + 'out', plan.att, res=plan.tok)),
+        'c_fc GEMM + QuickGELU': each_layer(lambda b: gemm(b + 'fc', plan.ln, act=1)),
+        'c_proj GEMM + residual': each_layer(lambda b: gemm(b + 'proj', plan.hid, res=plan.tok)),
+        'projection (rick_fc_f32)': lambda: run_fc(plan.post.data_ptr(), plan.head.data_ptr(), plan.head_bias.data_ptr(), plan.ws.data_ptr(),
+                                                   out.data_ptr(), n, c.width, c.dim, 0),
+    }
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--iters', type=int, default=20, help='forward passes per timed round')
+    ap.add_argument('--rounds', type=int, default=5)
+    args = ap.parse_args()
+    from rick_amd.clip import ClipImageFeatures, params_from_state_dict, torch_forward
+    from tests.clip_f64 import synthetic_clip_state_dict
+    torch.backends.cudnn.allow_tf32 = False
+    torch.backends.cuda.matmul.allow_tf32 = False
+    dev, size = 'cuda', 256
+    sd = synthetic_clip_state_dict(VIT_B32, 0)
+    params = params_from_state_dict(sd)
+    pd = {k: v.to(dev) for k, v in params.items()}
+    res = {'metric': 'clip_vit_b32'}
+    for n in (25, 100):
+        net = ClipImageFeatures(params, device=dev, batch=n)
+        cfg = net.cfg
+        x = torch.rand(n, 3, size, size, device=dev, generator=torch.Generator(dev).manual_seed(n)) * 2 - 1
+        hip = lambda: net(x)                                                  # noqa: E731
+        with torch.no_grad():
+            ref = lambda: torch_forward(pd, cfg, x)                           # noqa: E731
+            diff = float((hip() - ref()).abs().max() / ref().abs().max())
+            timed(hip, 3), timed(ref, 3)                                      # warm-up of both
+            th, tt = [], []
+            for _ in range(args.rounds):
+                th.append(timed(hip, args.iters))
+                tt.append(timed(ref, args.iters))
+        h, t = sorted(th)[len(th) // 2], sorted(tt)[len(tt) // 2]
+        res.update({f'hip_img_s_n{n}': n / h, f'torch_img_s_n{n}': n / t, f'hip_ms_n{n}': h * 1e3, f'torch_ms_n{n}': t * 1e3,
+                    f'max_rel_diff_vs_torch_n{n}': diff})
+        print(f'ViT-B/32 n={n:3d} from {size}^2: HIP kernels {n / h:8.1f} img/s ({h * 1e3:.2f} ms)   torch fp32 composition '
+              f'{n / t:8.1f} img/s ({t * 1e3:.2f} ms)   hip / torch = {h / t:.3f}   max rel diff {diff:.2e}')
+        print('    rounds (ms)  hip: ' + ' '.join(f'{v * 1e3:.2f}' for v in th) + '   torch: ' + ' '.join(f'{v * 1e3:.2f}' for v in tt))
+        total = 0.0
+        for name, fn in families(net, n, x).items():
+            tf = timed(fn, args.iters)
+            total += tf
+            res[f'family_ms_n{n}:{name}'] = tf * 1e3
+            print(f'    {name:36s} {tf * 1e3:8.3f} ms')
+        print(f'    {"sum of the families":36s} {total * 1e3:8.3f} ms', flush=True)
+        del net
+        torch.cuda.empty_cache()
+    print(json.dumps(res))
+
+
+if __name__ == '__main__':
+    main()
