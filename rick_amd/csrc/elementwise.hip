@@ -803,7 +803,8 @@ __global__ __launch_bounds__(256) void add_scale_kernel(const float *__restrict_
 }
 
 // y = (a + b) * alpha as fp32 AND as a split image (the ResBlock merge feeds the next block's convolutions), bound
-// |alpha| * (*amax_a + *amax_b).  Rows of C channels, C % 32 == 0.
+// |alpha| * (*amax_a + *amax_b).  Rows of C channels, C % 4 == 0 and 16-byte aligned pointers (the layout of
+// rick_split_pack_f32; the convolutions that consume the image check their own C % 32).
 __global__ __launch_bounds__(256) void add_scale_split_kernel(const float *__restrict__ a, const float *__restrict__ b,
                                                               float *__restrict__ y, unsigned char *__restrict__ sy,
                                                               cv_split_hdr *__restrict__ hdr, const float *__restrict__ ba,

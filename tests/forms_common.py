@@ -1,5 +1,5 @@
 """What the kernel-forms tests share (test_gpu_wgrad_forms.py, test_gpu_igemm_forms.py, test_gpu_convt2_forms.py,
-test_gpu_ufd_forms.py, test_gpu_mod_forms.py): guarded and fenced device buffers, the integer / 12-bit / scale generators of the exact modes, split images, the saturation counter, the
+test_gpu_ufd_forms.py, test_gpu_mod_forms.py, test_gpu_state_forms.py): guarded and fenced device buffers, the integer / 12-bit / scale generators of the exact modes, split images, the saturation counter, the
 NaN-fence and amax-word checks, the terms of the a-priori bound.  A plain module: no fixtures, no pytest hooks."""
 import ctypes
 import math
@@ -61,13 +61,13 @@ def scales(key, shape, mode):
 
 # ----------------------------------------------------------------------------------------------------- device helpers
 class Guarded:
-    """numel floats between two sentinel bands."""
+    """numel floats between two sentinel bands (`off` floats of extra offset misalign them: a slice of a flat buffer)."""
 
-    def __init__(self, numel, src=None):
-        self.buf = torch.full((PAD + numel + PAD,), SENT, device=DEV, dtype=torch.float32)
-        self.lo, self.hi = PAD, PAD + numel
+    def __init__(self, numel, src=None, off=0):
+        self.buf = torch.full((PAD + off + numel + PAD,), SENT, device=DEV, dtype=torch.float32)
+        self.lo, self.hi = PAD + off, PAD + off + numel
         self.v = self.buf[self.lo:self.hi]
-        assert self.v.data_ptr() % 16 == 0
+        assert self.v.data_ptr() % 16 == 4 * (off % 4)
         if src is not None:
             self.v.copy_(src.reshape(-1))
 
@@ -80,14 +80,15 @@ class Guarded:
 
 class Fenced:
     """An operand as a view into a larger buffer with NaN on both sides (`off` floats of extra offset misalign it): a read
-    outside the operand but inside the allocation poisons the result.  image = True: the fence is NaN as fp16 halves."""
+    outside the operand but inside the allocation poisons the result.  image = True: the fence is NaN as fp16 halves; `fill`:
+    another fence value, for operands that only pass through fmaxf (which drops a NaN: +inf there)."""
 
-    def __init__(self, numel, src=None, off=0, image=False):
+    def __init__(self, numel, src=None, off=0, image=False, fill=float('nan')):
         n4 = cdiv(numel, 4) * 4
         if image:
             self.buf = torch.full((PAD + off + n4 + PAD,), 0x7E007E00, device=DEV, dtype=torch.int32).view(torch.float32)
         else:
-            self.buf = torch.full((PAD + off + n4 + PAD,), float('nan'), device=DEV, dtype=torch.float32)
+            self.buf = torch.full((PAD + off + n4 + PAD,), fill, device=DEV, dtype=torch.float32)
         self.v = self.buf[PAD + off:PAD + off + numel]
         assert self.v.data_ptr() % 16 == 4 * (off % 4)
         if src is not None:
@@ -98,8 +99,8 @@ def p(gd):
     return None if gd is None else gd.v.data_ptr()
 
 
-def fenced(tn, off=0):
-    return None if tn is None else Fenced(tn.numel(), tn, off)
+def fenced(tn, off=0, fill=float('nan')):
+    return None if tn is None else Fenced(tn.numel(), tn, off, fill=fill)
 
 
 def stream():
