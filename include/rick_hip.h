@@ -711,8 +711,9 @@ int rick_fc_f32(const float *x, const float *wpk, const float *bias, float *ws, 
                 void *stream);
 
 /* ---------------------------------------------------------------------------------------
- * CLIP — the ViT image tower of CLIP (Radford et al., 2021; rick_amd/clip.py), forward only: unnormalised image embeddings
- * as `encode_image` returns them, for FID / KID in CLIP space and as the first step of the CLIP-guided adaptation recipes.
+ * CLIP — the ViT image tower of CLIP (Radford et al., 2021; rick_amd/clip.py): unnormalised image embeddings as
+ * `encode_image` returns them, for FID / KID in CLIP space, and their gradient with respect to the image (the weights are
+ * frozen: no weight gradients) for the CLIP-guided adaptation losses (rick_amd/clipguide.py).
  * Activations are fp32 rows [N * T][Wd] (T = G^2 + 1 tokens per image).
  * rick_clip_input_f32: planar x [N, 3, H, W] in [-1, 1] -> out [N, S, S, 4] (channel 3 = 0): F.interpolate(mode='bicubic',
  *   align_corners=False) to S x S (source s = (float(in) / float(S)) * (dst + 0.5) - 0.5, taps floor(s) - 1 .. floor(s) + 2
@@ -740,7 +741,35 @@ int rick_fc_f32(const float *x, const float *wpk, const float *bias, float *ws, 
  *   butterfly; p = e / den; out[c] = fmaf chain of p[k] v[k][c] over k ascending.  A query row's result depends on its own
  *   image and head only.
  * The projection runs on rick_fc_f32.  Unsupported shapes return 22.
- * No atomics: every output element has one writer and a fixed summation order (bit-identical from run to run). */
+ * No atomics: every output element has one writer and a fixed summation order (bit-identical from run to run).
+ * The data gradient.  The five GEMMs of the backward pass (c_proj, c_fc, out_proj, q/k/v with K = 3 Wd, the patch embedding
+ * onto 4 P^2 columns) are rick_inc_conv_lin_f32 on the transposed operand with a zero bias and act = 0; the projection's is
+ * rick_fc_f32 on the transposed head.  Around them:
+ * rick_clip_quickgelu_f32: out[i] = u[i] * (1 / (1 + expf(-(1.702f * u[i])))), the act = 1 epilogue's five operations as a
+ *   kernel of its own (the same bits), for a forward that keeps the pre-activation u.  out may be u.
+ * rick_clip_quickgelu_bwd_f32: out[i] = g[i] * (s + 1.702f * u[i] * s * (1 - s)), s = 1 / (1 + expf(-(1.702f * u[i]))).  out
+ *   may be g.
+ * rick_clip_layernorm_bwd_f32: rows x[r * ldx + c] (the forward's input), g[r * ldg + c] (the gradient of the forward's
+ *   output), w [C] -> out[r * ldo + c] = dx [+ add[r * ldo + c]]; add may be NULL or out.  Mean and rstd are recomputed in the
+ *   forward's order; xhat = (x - mean) rstd, gw = g w, m1 = sum gw / C (the lane's columns ascending, then the butterfly),
+ *   m2 = sum gw xhat / C (one fmaf chain per lane, then the butterfly), dx = rstd (gw - m1 - xhat m2).  No dw / db.  One wave
+ *   per row, C % 4 == 0, C <= 2048, every stride >= C and a multiple of 4.
+ * rick_clip_tokens_bwd_f32: the adjoint of rick_clip_tokens_f32 with respect to the patches: the same row gradient on
+ *   x = patches + pos[t] for the tokens t >= 1, g [N, T, C] -> out [N, T - 1, C] (the class row is dropped).
+ * rick_clip_attention_bwd_f32: qkv [N, T, 3 Wd] (the forward's input), g_out [N, T, Wd] -> g_qkv [N, T, 3 Wd]; stats
+ *   [N, heads, T, 3] is scratch (row maximum, denominator, delta).  Two launches of one block per (image, head).  One, a wave
+ *   per query row i with K and V in LDS: p recomputed by the forward's chain, dP_j = g_out_i . v_j (fmaf chain over c),
+ *   delta_i = sum_j p_j dP_j (per lane over its keys ascending, then the butterfly), dQ_i = scale sum_j p_j (dP_j - delta_i)
+ *   k_j (fmaf chain, j ascending).  Two, a wave per key row j with Q, g_out and the stats in LDS (up to 145 KB): p_ij =
+ *   expf(s_ij - max_i) / den_i, dV_j = sum_i p_ij g_out_i, dK_j = scale sum_i p_ij (dP_ij - delta_i) q_i, fmaf chains with i
+ *   ascending.  Nothing of size T x T goes to memory.  The forward's domain.
+ * rick_clip_input_bwd_f32: the adjoint of rick_clip_input_f32.  g [N G^2][(ky, kx, c4)], G = S / P, is the patch embedding's
+ *   data gradient in patch-row layout (pixel (G_y P + ky, G_x P + kx) of the S x S image); out [N, 3, H, W] planar.  Gather
+ *   form: a source pixel sums, over the destination pixels that tap it in ascending (row, column) order, fmaf(wy wx, g, .)
+ *   with the forward's fp32 weights (taps clamped onto one border pixel add their weights), then out = (sum * 0.5) / std_c.
+ *   Source pixels that no destination taps get exact zeros; at H == W == S the result is exactly g * 0.5 / std_c.  S % P == 0.
+ * All of them: one writer per output element, fixed summation order, a row's (image's) result independent of the other rows
+ * (images) of the launch, no host branch on device data. */
 int rick_clip_input_f32(const float *x, float *out, int N, int H, int W, int S, void *stream);
 int rick_inc_conv_lin_f32(const float *in, const float *wpk, const float *bias, const float *res, int act,
                           const rick_inc_conv *a, void *stream);
@@ -749,6 +778,15 @@ int rick_clip_tokens_f32(const float *patches, const float *cls, const float *po
 int rick_clip_layernorm_f32(const float *in, int64_t ldx, const float *w, const float *b, float *out, int R, int C, float eps,
                             void *stream);
 int rick_clip_attention_f32(const float *qkv, float *out, int N, int T, int heads, int D, void *stream);
+int rick_clip_quickgelu_f32(const float *u, float *out, int64_t n, void *stream);
+int rick_clip_quickgelu_bwd_f32(const float *u, const float *g, float *out, int64_t n, void *stream);
+int rick_clip_layernorm_bwd_f32(const float *x, int64_t ldx, const float *w, const float *g, int64_t ldg, const float *add,
+                                float *out, int64_t ldo, int R, int C, float eps, void *stream);
+int rick_clip_tokens_bwd_f32(const float *patches, const float *pos, const float *w, const float *g, float *out, int N, int T,
+                             int C, float eps, void *stream);
+int rick_clip_attention_bwd_f32(const float *qkv, const float *g_out, float *stats, float *g_qkv, int N, int T, int heads, int D,
+                                void *stream);
+int rick_clip_input_bwd_f32(const float *g, float *out, int N, int H, int W, int S, int P, void *stream);
 
 /* ---------------------------------------------------------------------------------------
  * Gram — the Gram matrix of a few very long rows and its adjoint (rick_amd/cdc.py): the device side of the cross-domain

@@ -238,6 +238,12 @@ SIGNATURES = {
     'rick_clip_tokens_f32': (c_int, [c_fp] * 6 + [c_int] * 3 + [c_f, c_fp]),
     'rick_clip_layernorm_f32': (c_int, [c_fp, c_i64, c_fp, c_fp, c_fp, c_int, c_int, c_f, c_fp]),
     'rick_clip_attention_f32': (c_int, [c_fp, c_fp, c_int, c_int, c_int, c_int, c_fp]),
+    'rick_clip_quickgelu_f32': (c_int, [c_fp, c_fp, c_i64, c_fp]),
+    'rick_clip_quickgelu_bwd_f32': (c_int, [c_fp, c_fp, c_fp, c_i64, c_fp]),
+    'rick_clip_layernorm_bwd_f32': (c_int, [c_fp, c_i64, c_fp, c_fp, c_i64, c_fp, c_fp, c_i64, c_int, c_int, c_f, c_fp]),
+    'rick_clip_tokens_bwd_f32': (c_int, [c_fp] * 5 + [c_int] * 3 + [c_f, c_fp]),
+    'rick_clip_attention_bwd_f32': (c_int, [c_fp] * 4 + [c_int] * 4 + [c_fp]),
+    'rick_clip_input_bwd_f32': (c_int, [c_fp, c_fp] + [c_int] * 5 + [c_fp]),
 }
 
 if not os.path.exists(LIB_PATH):

@@ -1,10 +1,18 @@
-"""CLIP's ViT image tower (Radford et al., 2021) on HIP kernels, forward only: the unnormalised image embeddings that
-``encode_image`` returns, for FID / KID in CLIP space and as the first step of the CLIP-guided adaptation recipes.
+"""CLIP's ViT image tower (Radford et al., 2021) on HIP kernels: the unnormalised image embeddings that ``encode_image``
+returns, for FID / KID in CLIP space, and their gradient with respect to the image for the CLIP-guided adaptation losses
+(rick_amd/clipguide.py).  The weights are frozen: there are no weight gradients.
 
     net = ClipImageFeatures.load(src, device='cuda', batch=25)       # src: a state_dict or a path, either layout below
     f = net(x)                                  # x [N, 3, H, W] fp32 in [-1, 1] -> [N, D] fp32 on x's device
     ev = Evaluator(g_ema, net, net(real_images))                     # FID (kid=True: KID) in CLIP space
     sim = clip_similarity(net(a), net(b))                            # rick_amd/evaluate.py
+    e = net.encode(x)                           # the same bits; differentiable (first order) with respect to x
+
+``encode`` keeps, per layer, what the backward pass reads (the residual stream before ln_1 and ln_2, q|k|v, the c_fc
+pre-activation) and runs the adjoint of every stage on HIP kernels: rick_clip_input_bwd_f32, rick_clip_tokens_bwd_f32,
+rick_clip_layernorm_bwd_f32, rick_clip_attention_bwd_f32, rick_clip_quickgelu_bwd_f32, the five data-gradient GEMMs of a
+layer on rick_inc_conv_lin_f32 over transposed operands, and the projection's on rick_fc_f32.  ``prepare_grad`` sizes that
+workspace; ``__call__`` is untouched by it.
 
 The network, per image:
 
@@ -180,9 +188,13 @@ def resize_affine(x, size):
 
 def torch_forward(p, cfg, x):
     """The whole network on x [N, 3, H, W] in the dtype and on the device of x and the parameters p -> [N, D]."""
+    return torch_tower(p, cfg, F.conv2d(resize_affine(x, cfg.size), p['conv1'], stride=cfg.patch).flatten(2).transpose(1, 2))
+
+
+def torch_tower(p, cfg, t):
+    """Steps 2 (from the patch rows t [n, G^2, Wd] on) to 5 of the network -> [n, D]."""
     wd, d = cfg.width, cfg.width // cfg.heads
-    n = x.shape[0]
-    t = F.conv2d(resize_affine(x, cfg.size), p['conv1'], stride=cfg.patch).flatten(2).transpose(1, 2)     # [n, G^2, Wd]
+    n = t.shape[0]
     t = torch.cat([p['cls'].expand(n, 1, wd), t], 1) + p['pos']
     t = F.layer_norm(t, (wd,), p['ln_pre.w'], p['ln_pre.b'], EPS)
     for i in range(cfg.layers):
@@ -206,6 +218,20 @@ def pack_patch_embedding(w, bn=None):
 def pack_linear(w, b, bn=None):
     """A linear layer W [out, in], b [out] as the 1 x 1 convolution's operand: wpk[k, o] = W[o, k].  (wpk, bias, Cop, bn)."""
     return gemm_conv.pack(w[:, :, None, None], b, bn=bn)
+
+
+def pack_linear_transposed(w, bn=None):
+    """The data gradient of a linear layer W [out, in] as a linear layer of its own: gx = gy W, so the operand is pack_linear's
+    of W^T [in, out] with a zero bias, wpk[o, k] = W[o, k].  (wpk, zero bias, Cop, bn)."""
+    return gemm_conv.pack(w.t()[:, :, None, None], None, bn=bn)
+
+
+def pack_patch_embedding_transposed(w, bn=None):
+    """The data gradient of the patch embedding: patch rows [N G^2, Wd] -> [N G^2, 4 P^2] in pack_patch_embedding's row order
+    (ky, kx, c4), a linear layer whose weight is that operand transposed (the rows of c = 3 are zero)."""
+    wd, _, p, _ = w.shape
+    rows = F.pad(w, (0, 0, 0, 0, 0, 1)).permute(2, 3, 1, 0).reshape(4 * p * p, wd)
+    return gemm_conv.pack(rows[:, :, None, None], None, bn=bn)
 
 
 def column_block(co, rows):
@@ -312,6 +338,182 @@ class _Plan:
                c.dim, 0)
 
 
+class _GradWorkspace:
+    """What a differentiable call (``ClipImageFeatures.encode``) needs beyond the forward plan, for `batch` images.
+
+    The transposed operands of the five GEMMs per layer and of the projection, packed once: about as much memory again as the
+    forward operands (0.35 GB at ViT-B/32).  The activations the backward pass reads, kept per layer: the residual stream
+    before ln_1 and before ln_2 (the residual GEMMs write a separate destination here instead of updating in place), q|k|v
+    and the c_fc pre-activation (c_fc runs with the identity epilogue, rick_clip_quickgelu_f32 follows: the same bits as the
+    fused epilogue), plus the patch rows: about 17 MB per image at ViT-B/32.  And the gradient buffers.  The forward scratch
+    (LayerNorm output, attention output, the activated hidden layer) is the plan's.  `version` counts forward runs: a backward
+    run whose activations were overwritten refuses."""
+
+    def __init__(self, plan, p, batch, device):
+        if batch < 1 or batch > plan.batch:
+            raise ValueError(f'{WHO}: grad_batch must be between 1 and batch = {plan.batch}')
+        self.plan, self.cfg, self.batch, self.version = plan, plan.cfg, int(batch), 0
+        self._lib = plan._lib
+        c, f32 = self.cfg, dict(device=device, dtype=torch.float32)
+        rows = batch * c.tokens
+        self.gemm = {}
+        self._add('patch', pack_patch_embedding_transposed(p['conv1'], column_block(4 * c.patch * c.patch, batch * (c.tokens - 1))),
+                  device)
+        for i in range(c.layers):
+            for name in ('qkv', 'out', 'fc', 'proj'):
+                w = p[f'blocks.{i}.{name}.w']
+                self._add(f'blocks.{i}.{name}', pack_linear_transposed(w, column_block(w.shape[1], rows)), device)
+        head_t = pack_fc_weight(p['head'].t().contiguous())
+        check_packed(head_t, c.dim, c.width, WHO)
+        self.head_t, self.head_t_bias = head_t.to(device), torch.zeros(c.width, **f32)
+        buf = lambda n: torch.empty(n, **f32)                                     # noqa: E731
+        self.x0, self.patches = buf(batch * c.size * c.size * 4), buf(batch * (c.tokens - 1) * c.width)
+        self.res = [buf(rows * c.width) for _ in range(2 * c.layers + 1)]
+        self.qkv = [buf(rows * 3 * c.width) for _ in range(c.layers)]
+        self.pre = [buf(rows * c.mlp) for _ in range(c.layers)]
+        self.gt, self.ga, self.gh, self.gq = buf(rows * c.width), buf(rows * c.width), buf(rows * c.mlp), buf(rows * 3 * c.width)
+        self.stats = buf(batch * c.heads * c.tokens * 3)
+        self.gpost, self.gp, self.gx0 = buf(batch * c.width), buf(batch * (c.tokens - 1) * c.width), buf(batch * c.size * c.size * 4)
+        self.ws = buf(self._lib.lib.rick_fc_workspace_floats(min(batch, FC_MAX_ROWS), c.dim, c.width))
+        self._desc = {}
+
+    def _add(self, name, packed, device):
+        wpk, bias, cop, bn = packed
+        self.gemm[name] = (wpk.to(device), bias.to(device), cop, bn)
+
+    def _descriptors(self, n):
+        """Forward ('f', name) and backward ('b', name) descriptors of every GEMM for n images, built once per n."""
+        if n not in self._desc:
+            c, pl, d = self.cfg, self.plan, {}
+            rows = n * c.tokens
+
+            def lin(table, name, k, co, dst):
+                _, _, cop, bn = table[name]
+                return gemm_conv.descriptor(rows, 1, 1, k, (1, 1), (1, 1), (0, 0), cop, bn, [(dst.data_ptr(), co, 0, co)])
+
+            _, _, cop, bn = pl.gemm['patch']
+            d['f', 'patch'] = gemm_conv.descriptor(n, c.size, c.size, 4, (c.patch, c.patch), (c.patch, c.patch), (0, 0), cop, bn,
+                                                   [(self.patches.data_ptr(), c.width, 0, c.width)])
+            _, _, cop, bn = self.gemm['patch']
+            k2 = 4 * c.patch * c.patch
+            d['b', 'patch'] = gemm_conv.descriptor(n * (c.tokens - 1), 1, 1, c.width, (1, 1), (1, 1), (0, 0), cop, bn,
+                                                   [(self.gx0.data_ptr(), k2, 0, k2)])
+            for i in range(c.layers):
+                b = f'blocks.{i}.'
+                d['f', b + 'qkv'] = lin(pl.gemm, b + 'qkv', c.width, 3 * c.width, self.qkv[i])
+                d['f', b + 'out'] = lin(pl.gemm, b + 'out', c.width, c.width, self.res[2 * i + 1])
+                d['f', b + 'fc'] = lin(pl.gemm, b + 'fc', c.width, c.mlp, self.pre[i])
+                d['f', b + 'proj'] = lin(pl.gemm, b + 'proj', c.mlp, c.width, self.res[2 * i + 2])
+                d['b', b + 'proj'] = lin(self.gemm, b + 'proj', c.width, c.mlp, self.gh)
+                d['b', b + 'fc'] = lin(self.gemm, b + 'fc', c.mlp, c.width, self.ga)
+                d['b', b + 'out'] = lin(self.gemm, b + 'out', c.width, c.width, self.ga)
+                d['b', b + 'qkv'] = lin(self.gemm, b + 'qkv', 3 * c.width, c.width, self.ga)
+            self._desc[n] = d
+        return self._desc[n]
+
+    def _gemm(self, table, desc, src, res=None):
+        L = self._lib
+        wpk, bias, _, _ = table
+        L.check(L.lib.rick_inc_conv_lin_f32(src.data_ptr(), wpk.data_ptr(), bias.data_ptr(), None if res is None else res.data_ptr(), 0,
+                                            desc, L.stream_ptr()), 'rick_inc_conv_lin_f32')
+
+    def forward(self, x, out):
+        """_Plan.run with the activations kept: x [n, 3, H, W] fp32 contiguous, n <= batch -> out [n, D], the same bits."""
+        L, c, pl = self._lib, self.cfg, self.plan
+        lib, stream = L.lib, L.stream_ptr()
+        n, _, H, W = x.shape
+        rows, d, v = n * c.tokens, self._descriptors(n), pl.vec
+        self.version += 1
+
+        def layernorm(name, src, ldx, dst, r):
+            L.check(lib.rick_clip_layernorm_f32(src.data_ptr(), ldx, v[name + '.w'].data_ptr(), v[name + '.b'].data_ptr(), dst.data_ptr(),
+                                                r, c.width, EPS, stream), 'rick_clip_layernorm_f32')
+
+        L.check(lib.rick_clip_input_f32(x.data_ptr(), self.x0.data_ptr(), n, H, W, c.size, stream), 'rick_clip_input_f32')
+        self._gemm(pl.gemm['patch'], d['f', 'patch'], self.x0)
+        L.check(lib.rick_clip_tokens_f32(self.patches.data_ptr(), v['cls'].data_ptr(), v['pos'].data_ptr(), v['ln_pre.w'].data_ptr(),
+                                         v['ln_pre.b'].data_ptr(), self.res[0].data_ptr(), n, c.tokens, c.width, EPS, stream),
+                'rick_clip_tokens_f32')
+        for i in range(c.layers):
+            b = f'blocks.{i}.'
+            t0, t1, t2 = self.res[2 * i:2 * i + 3]
+            layernorm(b + 'ln1', t0, c.width, pl.ln, rows)
+            self._gemm(pl.gemm[b + 'qkv'], d['f', b + 'qkv'], pl.ln)
+            L.check(lib.rick_clip_attention_f32(self.qkv[i].data_ptr(), pl.att.data_ptr(), n, c.tokens, c.heads, c.width // c.heads,
+                                                stream), 'rick_clip_attention_f32')
+            self._gemm(pl.gemm[b + 'out'], d['f', b + 'out'], pl.att, res=t0)
+            layernorm(b + 'ln2', t1, c.width, pl.ln, rows)
+            self._gemm(pl.gemm[b + 'fc'], d['f', b + 'fc'], pl.ln)                # the pre-activation, kept
+            L.check(lib.rick_clip_quickgelu_f32(self.pre[i].data_ptr(), pl.hid.data_ptr(), rows * c.mlp, stream), 'rick_clip_quickgelu_f32')
+            self._gemm(pl.gemm[b + 'proj'], d['f', b + 'proj'], pl.hid, res=t1)
+        layernorm('ln_post', self.res[-1], c.tokens * c.width, pl.post, n)
+        run_fc(pl.post.data_ptr(), pl.head.data_ptr(), pl.head_bias.data_ptr(), pl.ws.data_ptr(), out.data_ptr(), n, c.width, c.dim, 0)
+
+    def backward(self, go, gx):
+        """go [n, D] -> gx [n, 3, H, W], the gradient with respect to the images of the last forward run."""
+        L, c = self._lib, self.cfg
+        lib, stream = L.lib, L.stream_ptr()
+        n, _, H, W = gx.shape
+        rows, d, v = n * c.tokens, self._descriptors(n), self.plan.vec
+        wd = c.width
+
+        def layernorm_bwd(name, x, ldx, g, add, ld, r):
+            L.check(lib.rick_clip_layernorm_bwd_f32(x.data_ptr(), ldx, v[name + '.w'].data_ptr(), g.data_ptr(), wd,
+                                                    None if add is None else add.data_ptr(), self.gt.data_ptr(), ld, r, wd, EPS, stream),
+                    'rick_clip_layernorm_bwd_f32')
+
+        run_fc(go.data_ptr(), self.head_t.data_ptr(), self.head_t_bias.data_ptr(), self.ws.data_ptr(), self.gpost.data_ptr(), n, c.dim, wd,
+               0)
+        self.gt[:rows * wd].zero_()                           # ln_post saw token 0 only
+        layernorm_bwd('ln_post', self.res[-1], c.tokens * wd, self.gpost, None, c.tokens * wd, n)
+        for i in reversed(range(c.layers)):
+            b = f'blocks.{i}.'
+            self._gemm(self.gemm[b + 'proj'], d['b', b + 'proj'], self.gt)
+            L.check(lib.rick_clip_quickgelu_bwd_f32(self.pre[i].data_ptr(), self.gh.data_ptr(), self.gh.data_ptr(), rows * c.mlp, stream),
+                    'rick_clip_quickgelu_bwd_f32')
+            self._gemm(self.gemm[b + 'fc'], d['b', b + 'fc'], self.gh)
+            layernorm_bwd(b + 'ln2', self.res[2 * i + 1], wd, self.ga, self.gt, wd, rows)
+            self._gemm(self.gemm[b + 'out'], d['b', b + 'out'], self.gt)
+            L.check(lib.rick_clip_attention_bwd_f32(self.qkv[i].data_ptr(), self.ga.data_ptr(), self.stats.data_ptr(), self.gq.data_ptr(),
+                                                    n, c.tokens, c.heads, wd // c.heads, stream), 'rick_clip_attention_bwd_f32')
+            self._gemm(self.gemm[b + 'qkv'], d['b', b + 'qkv'], self.gq)
+            layernorm_bwd(b + 'ln1', self.res[2 * i], wd, self.ga, self.gt, wd, rows)
+        L.check(lib.rick_clip_tokens_bwd_f32(self.patches.data_ptr(), v['pos'].data_ptr(), v['ln_pre.w'].data_ptr(), self.gt.data_ptr(),
+                                             self.gp.data_ptr(), n, c.tokens, wd, EPS, stream), 'rick_clip_tokens_bwd_f32')
+        self._gemm(self.gemm['patch'], d['b', 'patch'], self.gp)
+        L.check(lib.rick_clip_input_bwd_f32(self.gx0.data_ptr(), gx.data_ptr(), n, H, W, c.size, c.patch, stream), 'rick_clip_input_bwd_f32')
+
+
+class _Encode(torch.autograd.Function):
+    """[N, D] embeddings of x; the gradient with respect to x on the HIP backward kernels."""
+
+    @staticmethod
+    def forward(ctx, x, net):
+        ws = net._grad_workspace()
+        x = x.contiguous()
+        out = torch.empty((x.shape[0], net.cfg.dim), device=x.device, dtype=torch.float32)
+        with torch.cuda.device(net.device):
+            ws.forward(x, out)
+        ctx.net, ctx.ws, ctx.version, ctx.shape = net, ws, ws.version, tuple(x.shape)
+        return out
+
+    @staticmethod
+    def backward(ctx, go):
+        if torch.is_grad_enabled():
+            raise RuntimeError(f'{WHO}.encode: the backward pass is first order only (create_graph=True is not supported)')
+        ws = ctx.net._grad_workspace()
+        if ws is not ctx.ws or ws.version != ctx.version:
+            raise RuntimeError(f'{WHO}.encode: the stored activations were overwritten by a later differentiable call; '
+                               f'run backward before the next {WHO}.encode on this network')
+        if go.device != ctx.net.device or go.dtype != torch.float32:
+            raise RuntimeError(f'{WHO}.encode: upstream gradient on {go.device} / {go.dtype}')
+        go = go.contiguous()
+        gx = torch.empty(ctx.shape, device=go.device, dtype=torch.float32)
+        with torch.cuda.device(ctx.net.device):
+            ws.backward(go, gx)
+        return gx, None
+
+
 class ClipImageFeatures:
     """CLIP's ViT image tower up to the projection (unnormalised embeddings) on HIP kernels; see the module docstring."""
 
@@ -321,7 +523,7 @@ class ClipImageFeatures:
         self.params, self.cfg = params, config_from_params(params, heads)
         self.batch = int(batch)
         self.device = cuda_device(device)
-        self._plan = None
+        self._plan, self._grad_ws = None, None
         if self.device.type == 'cuda':
             with torch.cuda.device(self.device):
                 self._plan = _Plan(params, self.cfg, self.batch, self.device)
@@ -348,3 +550,37 @@ class ClipImageFeatures:
                 hi = min(N, lo + self.batch)
                 self._plan.run(x[lo:hi], out[lo:hi])
         return out
+
+    def prepare_grad(self, grad_batch=8):
+        """Builds what ``encode`` needs for up to `grad_batch` images per differentiable call (at most `batch`): the transposed
+        GEMM operands, packed once (about as much device memory again as the forward operands, 0.35 GB at ViT-B/32), one set of
+        stored activations (about 17 MB per image at ViT-B/32) and the gradient buffers.  ``encode`` calls it with the default
+        on first use.  ``__call__`` is not affected: same plan, same launches."""
+        if self._plan is None:
+            raise RuntimeError(f'{WHO}: prepare_grad needs a network loaded for a GPU (CPU tensors use torch autograd)')
+        if self._grad_ws is None or self._grad_ws.batch != int(grad_batch):
+            with torch.cuda.device(self.device):
+                self._grad_ws = _GradWorkspace(self._plan, self.params, int(grad_batch), self.device)
+        return self
+
+    def _grad_workspace(self):
+        if self._grad_ws is None:
+            self.prepare_grad(min(8, self.batch))
+        return self._grad_ws
+
+    def encode(self, x):
+        """``__call__``'s values, bit for bit, differentiable with respect to x when x requires grad (otherwise it IS
+        ``__call__``).  First order only: ``create_graph=True`` raises in the backward pass.  CUDA tensors run the HIP backward
+        kernels over one set of stored activations (``prepare_grad``): a differentiable call of more than grad_batch images
+        raises (it is not chunked), and a backward pass must run before the next differentiable call on this network.  The
+        weights are frozen: the only gradient is the image's.  CPU tensors take torch autograd through ``torch_forward``."""
+        check_images(x, WHO, self.device)
+        if not (x.requires_grad and torch.is_grad_enabled()):
+            return self(x)
+        if x.device.type == 'cpu':
+            return torch_forward(self.params, self.cfg, x)
+        ws = self._grad_workspace()
+        if x.shape[0] > ws.batch:
+            raise ValueError(f'{WHO}.encode: {x.shape[0]} images in a differentiable call, grad_batch is {ws.batch} '
+                             f'(prepare_grad(grad_batch=...); the call is not chunked)')
+        return _Encode.apply(x, self)

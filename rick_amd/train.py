@@ -228,6 +228,9 @@ class TrainConfig:
     subspace_std: float = 0.05                       # --subspace_std (:721)
     feat_ind: int = 3                                # --feat_ind (:709): p_ind is drawn from the first feat_ind taps
     n_anchors: int = 10                              # rows of the anchor matrix drawn at construction
+    clip_dir_weight: float = 0.0                     # StyleGAN-NADA's directional loss in CLIP space (rick_amd/clipguide.py); 0 = off
+    clip_within_weight: float = 0.0                  # Mind-the-Gap's in-domain consistency loss in CLIP space; 0 = off
+    clip_batch: int = 4                              # the CLIP terms' own latent batch (like cdc_batch)
 
 
 class AdaController:
@@ -331,11 +334,23 @@ class RickTrainer:
     anchor of the elastic-weight-consolidation term (required when cfg.ewc_weight > 0), given as what `set_ewc` takes: a pair
     (source_state, fisher) of {name: tensor} mappings, fisher None for the L2-SP penalty.  `patch_heads`: the
     rick_amd.patchd.PatchHeads of CDC's patch-level discriminator (cfg.subspace_freq > 0; built here when None).  Deviation from
-    CDC as recalled: R1 stays on the image-level logits, where CDC sends it through the patch head on patch iterations."""
+    CDC as recalled: R1 stays on the image-level logits, where CDC sends it through the patch head on patch iterations.
+    `clip`: the rick_amd.clipguide.ClipGuide (encoder and direction) of the CLIP-space terms, required with g_source when
+    cfg.clip_dir_weight or cfg.clip_within_weight > 0; with both at 0 it is never used."""
 
     def __init__(self, cfg, generator, discriminator, g_ema, d_ema, dp=None, g_source=None, ewc=None, d_source=None,
-                 patch_heads=None):
+                 patch_heads=None, clip=None):
         self.cfg, self.g, self.d, self.g_ema, self.d_ema, self.dp = cfg, generator, discriminator, g_ema, d_ema, dp
+        for w in (cfg.clip_dir_weight, cfg.clip_within_weight):
+            if w < 0 or not math.isfinite(w):
+                raise ValueError('RickTrainer: clip_dir_weight and clip_within_weight must be finite and >= 0')
+        self.clip = clip
+        if cfg.clip_dir_weight > 0 or cfg.clip_within_weight > 0:
+            if g_source is None or clip is None:
+                raise ValueError('RickTrainer: clip_dir_weight / clip_within_weight > 0 need the frozen source generator and the '
+                                 'CLIP guide (g_source=, clip=ClipGuide(net, direction))')
+            if cfg.clip_batch < (2 if cfg.clip_within_weight > 0 else 1):
+                raise ValueError('RickTrainer: clip_batch must be >= 1, and >= 2 with clip_within_weight > 0')
         # the discriminator-side augmentation: DiffAugment (cfg.diffaug) or ADA (cfg.augment), never both; None when both are off
         self._augmenter = AdaAugmenter(self) if cfg.augment else None
         if cfg.diffaug:
@@ -1005,21 +1020,36 @@ class RickTrainer:
             out['dcl_g'] = self._dcl_g_term(dcl_noise, dcl_layers, g_noise)
         return out
 
+    def _clip_terms(self, clip_noise=None, g_noise=None):
+        """The unweighted CLIP-space terms (rick_amd/clipguide.py) of one draw: z ~ N(0, I) [clip_batch, latent] through the
+        frozen source generator (no grad) and through G with the same noise maps, both image batches through the encoder."""
+        cfg = self.cfg
+        z = clip_noise if clip_noise is not None else torch.randn(cfg.clip_batch, cfg.latent, device=self.device)
+        if g_noise is None:
+            g_noise = [n.expand(z.shape[0], -1, -1, -1).clone().normal_() for n in self.g.make_noise()]
+        with torch.no_grad():
+            fake_s, _ = self.g_source([z], noise=g_noise)
+        fake_t, _ = self.g([z], noise=g_noise)
+        return self.clip.terms(fake_t, fake_s, cfg.clip_dir_weight > 0, cfg.clip_within_weight > 0)
+
     def g_step(self, noise, g_noise=None, graph=False, cdc_noise=None, cdc_layers=None, dcl_noise=None, dcl_layers=None,
-               patch=None):
+               patch=None, clip_noise=None):
         """Non-saturating G step.  With cfg.cdc_weight > 0 the distance-consistency term is added before the one backward():
         its drawn layers change the launch list from step to step, so such a step is never captured — `graph=True` then runs
         the eager path (its own mixing noise, no step graph) while every other step type keeps replaying.  `cdc_noise`
         [cdc_batch, latent] and `cdc_layers` fix the term's draws (tests); `g_noise` also fixes its noise maps.  The generator
         contrastive term (cfg.dcl_g_weight > 0, `dcl_noise` / `dcl_layers`) is treated the same way, and so is every G step with
         cfg.subspace_freq > 0 (rick_amd/patchd.py): `patch=p_ind` takes the non-saturating loss over the patch map of
-        patchd.patch_logits at that tap; neither the discriminator nor the heads get gradients."""
+        patchd.patch_logits at that tap; neither the discriminator nor the heads get gradients.  The CLIP-space terms
+        (cfg.clip_dir_weight / cfg.clip_within_weight > 0, rick_amd/clipguide.py) are added the same way and also run eagerly;
+        `clip_noise` [clip_batch, latent] fixes their latents, `g_noise` their noise maps."""
         cdc_on = self.cfg.cdc_weight > 0
+        clip_on = self.cfg.clip_dir_weight > 0 or self.cfg.clip_within_weight > 0
         dcl_on = self.cfg.dcl_g_weight > 0
         patch_on = self.cfg.subspace_freq > 0
         if patch is not None and not patch_on:
             raise ValueError('RickTrainer.g_step: patch= needs cfg.subspace_freq > 0')
-        if (cdc_on or dcl_on or patch_on) and graph:
+        if (cdc_on or dcl_on or patch_on or clip_on) and graph:
             graph = False
             if noise is None:
                 noise = mixing_noise(self.cfg.batch, self.cfg.latent, self.cfg.mixing, self.device)
@@ -1055,6 +1085,12 @@ class RickTrainer:
                 elif dcl_on:
                     terms = self._consistency_terms(cdc_noise, cdc_layers, dcl_noise, dcl_layers, g_noise)
                     for name, weight in (('cdc', self.cfg.cdc_weight), ('dcl_g', self.cfg.dcl_g_weight)):
+                        if name in terms:
+                            total = total + weight * terms[name]
+                            self.losses[name] = terms[name].detach()
+                if clip_on:
+                    terms = self._clip_terms(clip_noise, g_noise)
+                    for name, weight in (('clip_dir', self.cfg.clip_dir_weight), ('clip_within', self.cfg.clip_within_weight)):
                         if name in terms:
                             total = total + weight * terms[name]
                             self.losses[name] = terms[name].detach()

@@ -5,12 +5,15 @@ computation as an fp32 torch composition on the GPU (rick_amd.clip.torch_forward
 tensors).  Seeded synthetic weights (timing only).
 
   python tools/bench_clip.py [--iters 20] [--rounds 5]
+  python tools/bench_clip.py --backward      forward + backward of ClipImageFeatures.encode at n = 4, 8 and 25 against the fp32
+                                             torch autograd composition on the same GPU, and the backward pass per kernel family
 The two implementations are timed alternately, `--rounds` times each after a warm-up of both; the report gives the median
 and every round.  Prints a readable report and one JSON line."""
 import argparse
 import json
 import os
 import sys
+import time
 
 import torch
 
@@ -78,11 +81,118 @@ def families(net, n, x):
     }
 
 
+def backward_families(net, n):
+    """{family: a function that issues that family's launches of one backward pass of n images}, on the gradient workspace's
+    buffers after a differentiable forward run."""
+    from rick_amd import _lib as L
+    from rick_amd.clip import EPS
+    from rick_amd.fc import run_fc
+    ws, c, lib = net._grad_workspace(), net.cfg, L.lib
+    d, v, rows, wd = ws._descriptors(n), net._plan.vec, n * c.tokens, c.width
+    gx, go = torch.empty(n, 3, 256, 256, device=ws.gt.device), torch.ones(n, c.dim, device=ws.gt.device)
+
+    def ln_bwd(name, x, ldx, g, add, ld, r):
+        L.check(lib.rick_clip_layernorm_bwd_f32(x.data_ptr(), ldx, v[name + '.w'].data_ptr(), g.data_ptr(), wd,
+                                                None if add is None else add.data_ptr(), ws.gt.data_ptr(), ld, r, wd, EPS, L.stream_ptr()),
+                'rick_clip_layernorm_bwd_f32')
+
+    def layernorms():
+        ln_bwd('ln_post', ws.res[-1], c.tokens * wd, ws.gpost, None, c.tokens * wd, n)
+        for i in range(c.layers):
+            ln_bwd(f'blocks.{i}.ln2', ws.res[2 * i + 1], wd, ws.ga, ws.gt, wd, rows)
+            ln_bwd(f'blocks.{i}.ln1', ws.res[2 * i], wd, ws.ga, ws.gt, wd, rows)
+
+    def each_layer(fn):
+        return lambda: [fn(i, f'blocks.{i}.') for i in range(c.layers)]
+
+    gemm = lambda name, src: ws._gemm(ws.gemm[name], d['b', name], src)        # noqa: E731
+    return {
+        'projection^T (rick_fc_f32)': lambda: run_fc(go.data_ptr(), ws.head_t.data_ptr(), ws.head_t_bias.data_ptr(), ws.ws.data_ptr(),
+                                                     ws.gpost.data_ptr(), n, c.dim, wd, 0),
+        'LayerNorm backward (2 per layer + ln_post)': layernorms,
+        'c_proj^T GEMM': each_layer(lambda i, b: gemm(b + 'proj', ws.gt)),
+        'QuickGELU derivative': each_layer(lambda i, b: L.check(lib.rick_clip_quickgelu_bwd_f32(
+            ws.pre[i].data_ptr(), ws.gh.data_ptr(), ws.gh.data_ptr(), rows * c.mlp, L.stream_ptr()), 'rick_clip_quickgelu_bwd_f32')),
+        'c_fc^T GEMM': each_layer(lambda i, b: gemm(b + 'fc', ws.gh)),
+        'out_proj^T GEMM': each_layer(lambda i, b: gemm(b + 'out', ws.gt)),
+        'attention backward (2 launches)': each_layer(lambda i, b: L.check(lib.rick_clip_attention_bwd_f32(
+            ws.qkv[i].data_ptr(), ws.ga.data_ptr(), ws.stats.data_ptr(), ws.gq.data_ptr(), n, c.tokens, c.heads, wd // c.heads,
+            L.stream_ptr()), 'rick_clip_attention_bwd_f32')),
+        'q/k/v^T GEMM (K = 3 Wd)': each_layer(lambda i, b: gemm(b + 'qkv', ws.gq)),
+        'tokens + ln_pre adjoint': lambda: L.check(lib.rick_clip_tokens_bwd_f32(
+            ws.patches.data_ptr(), v['pos'].data_ptr(), v['ln_pre.w'].data_ptr(), ws.gt.data_ptr(), ws.gp.data_ptr(), n, c.tokens, wd, EPS,
+            L.stream_ptr()), 'rick_clip_tokens_bwd_f32'),
+        'patch embedding^T GEMM': lambda: gemm('patch', ws.gp),
+        'input adjoint (bicubic + affine)': lambda: L.check(lib.rick_clip_input_bwd_f32(
+            ws.gx0.data_ptr(), gx.data_ptr(), n, 256, 256, c.size, c.patch, L.stream_ptr()), 'rick_clip_input_bwd_f32'),
+    }
+
+
+def torch_reference(p, cfg, x):
+    """rick_amd.clip.torch_forward with the patch embedding as a reshape and a matrix product: the same fp32 sums of products
+    without a convolution, whose backward pass would first send the library on a search for a 32 x 32 stride-32 kernel."""
+    from rick_amd.clip import resize_affine, torch_tower
+    n, g, k = x.shape[0], cfg.grid, cfg.patch
+    rows = resize_affine(x, cfg.size).reshape(n, 3, g, k, g, k).permute(0, 2, 4, 1, 3, 5).reshape(n, g * g, 3 * k * k)
+    return torch_tower(p, cfg, rows @ p['conv1'].reshape(cfg.width, -1).t())
+
+
+def main_backward(args):
+    from rick_amd.clip import ClipImageFeatures, params_from_state_dict
+    from tests.clip_f64 import synthetic_clip_state_dict
+    torch.backends.cudnn.allow_tf32 = False
+    torch.backends.cuda.matmul.allow_tf32 = False
+    dev, size = 'cuda', 256
+    params = params_from_state_dict(synthetic_clip_state_dict(VIT_B32, 0))
+    pd = {k: v.to(dev) for k, v in params.items()}
+    res = {'metric': 'clip_vit_b32_backward'}
+    for n in args.n:
+        t0 = time.time()
+        net = ClipImageFeatures(params, device=dev, batch=n).prepare_grad(grad_batch=n)
+        cfg = net.cfg
+        gen = torch.Generator(dev).manual_seed(n)
+        x = (torch.rand(n, 3, size, size, device=dev, generator=gen) * 2 - 1).requires_grad_()
+        r = torch.randn(n, cfg.dim, device=dev, generator=gen)
+        hip = lambda: torch.autograd.grad((net.encode(x) * r).sum(), x)[0]                    # noqa: E731
+        ref = lambda: torch.autograd.grad((torch_reference(pd, cfg, x) * r).sum(), x)[0]      # noqa: E731
+        fwd = lambda: net(x.detach())                                                          # noqa: E731
+        gh, gt = hip(), ref()
+        diff = float((gh - gt).abs().max() / gt.abs().max())
+        print(f'n={n}: set up, first pass of both in {time.time() - t0:.1f} s', flush=True)
+        timed(hip, 3), timed(ref, 3)                                          # warm-up of both
+        th, tt = [], []
+        for _ in range(args.rounds):
+            th.append(timed(hip, args.iters))
+            tt.append(timed(ref, args.iters))
+        h, t, f = sorted(th)[len(th) // 2], sorted(tt)[len(tt) // 2], timed(fwd, args.iters)
+        res.update({f'hip_fwd_bwd_ms_n{n}': h * 1e3, f'torch_fwd_bwd_ms_n{n}': t * 1e3, f'hip_fwd_only_ms_n{n}': f * 1e3,
+                    f'max_rel_grad_diff_vs_torch_n{n}': diff})
+        print(f'ViT-B/32 n={n:3d} from {size}^2, forward + backward: HIP kernels {h * 1e3:.2f} ms ({n / h:7.1f} img/s)   torch fp32 autograd '
+              f'{t * 1e3:.2f} ms ({n / t:7.1f} img/s)   hip / torch = {h / t:.3f}   forward only (__call__) {f * 1e3:.2f} ms   '
+              f'max rel gradient diff {diff:.2e}')
+        print('    rounds (ms)  hip: ' + ' '.join(f'{v * 1e3:.2f}' for v in th) + '   torch: ' + ' '.join(f'{v * 1e3:.2f}' for v in tt))
+        hip()                                                                 # valid activations and gradients in the workspace
+        total = 0.0
+        for name, fn in backward_families(net, n).items():
+            tf = timed(fn, args.iters)
+            total += tf
+            res[f'bwd_family_ms_n{n}:{name}'] = tf * 1e3
+            print(f'    {name:44s} {tf * 1e3:8.3f} ms')
+        print(f'    {"sum of the backward families":44s} {total * 1e3:8.3f} ms', flush=True)
+        del net
+        torch.cuda.empty_cache()
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--iters', type=int, default=20, help='forward passes per timed round')
+    ap.add_argument('--iters', type=int, default=20, help='passes per timed round')
     ap.add_argument('--rounds', type=int, default=5)
+    ap.add_argument('--backward', action='store_true', help='time forward + backward of encode instead')
+    ap.add_argument('--n', type=int, nargs='+', default=[4, 8, 25], help='batch sizes of --backward')
     args = ap.parse_args()
+    if args.backward:
+        return main_backward(args)
     from rick_amd.clip import ClipImageFeatures, params_from_state_dict, torch_forward
     from tests.clip_f64 import synthetic_clip_state_dict
     torch.backends.cudnn.allow_tf32 = False
