@@ -768,8 +768,29 @@ int rick_fc_f32(const float *x, const float *wpk, const float *bias, float *ws, 
  *   form: a source pixel sums, over the destination pixels that tap it in ascending (row, column) order, fmaf(wy wx, g, .)
  *   with the forward's fp32 weights (taps clamped onto one border pixel add their weights), then out = (sum * 0.5) / std_c.
  *   Source pixels that no destination taps get exact zeros; at H == W == S the result is exactly g * 0.5 / std_c.  S % P == 0.
- * All of them: one writer per output element, fixed summation order, a row's (image's) result independent of the other rows
- * (images) of the launch, no host branch on device data. */
+ * The text tower (rick_amd/cliptext.py), forward only: its weights are frozen and its input is discrete.  It shares
+ * rick_inc_conv_lin_f32, rick_clip_layernorm_f32 and rick_fc_f32 with the image tower; rows are [N * T][Wd], T positions per prompt.
+ * rick_clip_text_tokens_f32: ids [N, T] int32, table [V, C], pos [T, C] -> out[n, t, :] = table[ids[n, t]] + pos[t], one fp32
+ *   add per element, 16-byte accesses.  C % 4 == 0, C <= 2048, 1 <= T <= 257, V >= 1, N T C / 1024 (the blocks of the launch)
+ *   below 2^31.  The ids are device memory: the host
+ *   validates 0 <= id < V before upload, and the kernel forces every id into [0, V), so no launch reads outside the table.
+ * rick_clip_attention_causal_f32: rick_clip_attention_f32 (the same kernel template: layout, LDS staging, key ownership, fmaf
+ *   chains, butterfly, softmax form, domain) with query row i seeing the keys k <= i only.  A masked slot holds -inf before the
+ *   maximum and adds an exact 0.f to the denominator, as a slot k >= T does in the unmasked kernel; the P V chain runs k = 0 ... i
+ *   ascending.  Row i of a prompt of T tokens is therefore bit-identical to row i of rick_clip_attention_f32 on the first i + 1
+ *   tokens, and depends on the rows <= i of its own prompt and head alone.  The score chains behind the diagonal are not run.
+ * rick_clip_layernorm_rows_f32: in holds rows of C floats (compact), idx [R] int32 row numbers (device memory, any order,
+ *   repeats allowed) -> out [R, C] = LayerNorm of row idx[r], the arithmetic of rick_clip_layernorm_f32 and the same bits as
+ *   that entry on the same rows gathered contiguously.  The entry takes no row count and cannot read idx, so it CANNOT bound
+ *   an index from above (a negative one is read as 0): a caller that passes an index past the rows of `in` makes the kernel
+ *   read out of bounds.  Checking idx on the host before its upload is the caller's duty (rick_amd/cliptext.py check_rows).
+ * All of them: one writer per output element, fixed summation order, a row's (image's, prompt's) result independent of the other
+ * rows (images, prompts) of the launch, no host branch on device data. */
+int rick_clip_text_tokens_f32(const int32_t *ids, const float *table, const float *pos, float *out, int N, int T, int V, int C,
+                              void *stream);
+int rick_clip_attention_causal_f32(const float *qkv, float *out, int N, int T, int heads, int D, void *stream);
+int rick_clip_layernorm_rows_f32(const float *in, const int32_t *idx, const float *w, const float *b, float *out, int R, int C,
+                                 float eps, void *stream);
 int rick_clip_input_f32(const float *x, float *out, int N, int H, int W, int S, void *stream);
 int rick_inc_conv_lin_f32(const float *in, const float *wpk, const float *bias, const float *res, int act,
                           const rick_inc_conv *a, void *stream);

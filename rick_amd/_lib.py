@@ -244,6 +244,9 @@ SIGNATURES = {
     'rick_clip_tokens_bwd_f32': (c_int, [c_fp] * 5 + [c_int] * 3 + [c_f, c_fp]),
     'rick_clip_attention_bwd_f32': (c_int, [c_fp] * 4 + [c_int] * 4 + [c_fp]),
     'rick_clip_input_bwd_f32': (c_int, [c_fp, c_fp] + [c_int] * 5 + [c_fp]),
+    'rick_clip_text_tokens_f32': (c_int, [c_fp] * 4 + [c_int] * 4 + [c_fp]),
+    'rick_clip_attention_causal_f32': (c_int, [c_fp, c_fp, c_int, c_int, c_int, c_int, c_fp]),
+    'rick_clip_layernorm_rows_f32': (c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_f, c_fp]),
 }
 
 if not os.path.exists(LIB_PATH):

@@ -10,12 +10,16 @@ recalled, unverified against the papers' code.
     loss = directional_loss(e_t, e_s, direction) + within_loss(e_t, e_s)
 
 The heads act on [N, D] embeddings: a few thousand numbers, plain fp32 torch compositions on the embeddings' device.  The hot
-path is ``ClipImageFeatures.encode``'s backward pass (HIP kernels, include/rick_hip.h "CLIP").  There is no text tower here:
-wherever a direction is expected, any [D] vector is accepted, so a text-derived one can be supplied from outside.
+path is ``ClipImageFeatures.encode``'s backward pass (HIP kernels, include/rick_hip.h "CLIP").  Wherever a direction is
+expected, any [D] vector is accepted: ``domain_direction`` derives one from two image sets, ``text_direction`` from two
+prompts through the text tower (rick_amd/cliptext.py, rick_amd/cliptok.py).
+
+    direction = text_direction(ClipTextFeatures.load(src), ClipTokenizer.load(vocab_json, merges_txt), 'photo', 'sketch')
 
 With n(e) = e / |e| and cos = F.cosine_similarity (eps 1e-8):
 
 * domain_direction = n(mean_i n(e(target_i)) - mean_i n(e(source_i)));
+* text_direction = n(mean_t n(E(template_t(target))) - mean_t n(E(template_t(source)))), E the text tower;
 * directional_loss = mean_i (1 - cos(n(e_t,i) - n(e_s,i), direction));
 * within_loss = mean over pairs i < j of 1 - cos(n(e_s,i) - n(e_s,j), n(e_t,i) - n(e_t,j)).
 """
@@ -36,6 +40,23 @@ def domain_direction(net, source_images, target_images):
     """[D] fp32 unit vector from the source set's mean normalised embedding to the target set's; no gradient."""
     means = [F.normalize(net(x).float(), dim=1, eps=0).mean(0) for x in (source_images, target_images)]
     return F.normalize(means[1] - means[0], dim=0, eps=0)
+
+
+@torch.no_grad()
+def text_direction(tnet, tok, source, target, templates=('a photo of a {}.',)):
+    """[D] fp32 unit vector from the source word's mean normalised text embedding over the templates to the target word's, on
+    the text tower's device; no gradient.  tnet: ClipTextFeatures, tok: ClipTokenizer (any callable from a list of strings to
+    id rows)."""
+    if not templates:
+        raise ValueError(f'{WHO}: text_direction needs at least one template')
+    means = []
+    for word in (source, target):
+        ids = tok([t.format(word) for t in templates])
+        means.append(F.normalize(tnet(ids.to(tnet.device)).float(), dim=1, eps=0).mean(0))
+    direction = F.normalize(means[1] - means[0], dim=0, eps=0)
+    if not torch.isfinite(direction).all():
+        raise ValueError(f'{WHO}: the embeddings of {source!r} and {target!r} coincide: no direction between them')
+    return direction
 
 
 def directional_loss(e_t, e_s, direction):

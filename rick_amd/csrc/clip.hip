@@ -5,6 +5,10 @@
 // attention and QuickGELU as a kernel of its own, each with its adjoint with respect to the data.  Activations are fp32 rows
 // [tokens][width].  Every output element is written by exactly one thread with a fixed summation order: no atomics, run-to-run
 // bit-identical, and an image's values do not depend on the other images of the call.
+//
+// The text tower (rick_amd/cliptext.py, forward only) shares the GEMMs, the LayerNorm and the attention kernel, the last with
+// a causal mask as a compile-time flag, and adds the token-embedding lookup and a LayerNorm of rows picked by index (ln_final
+// on each prompt's EOT row).
 #include "common.h"
 
 #define CL_MAXJ 8              // a row of up to 2048 columns in registers: lane l holds columns 4 l + 256 j, j < 8
@@ -157,7 +161,12 @@ __device__ __forceinline__ float cl_wave_max(float v) {
 
 static size_t cl_attention_lds(int T, int D) { return sizeof(float) * ((size_t)T * D + (size_t)T * (D + 1) + 4 * (size_t)((T + 3) & ~3)); }
 
-template <int D>
+// CAUSAL (the text tower): query row i sees the keys k <= i.  With lim = i + 1 in the place of T in everything a row does, row i
+// runs the arithmetic of the non-causal kernel on the first i + 1 tokens, operation for operation: the slots k >= lim hold
+// -inf before the maximum and an exact 0.f in the denominator, as the slots k >= T do there, and the P V chain ends at k = i.
+// So row i is bit-identical to row i of rick_clip_attention_f32 on the first i + 1 tokens.  The score chains of the keys
+// behind the diagonal are not run (a 64-key slot that lies wholly behind it is skipped by the whole wave).
+template <int D, bool CAUSAL>
 __global__ __launch_bounds__(256) void clip_attention_kernel(const float *__restrict__ qkv, float *__restrict__ out, int T, int Wd,
                                                              int heads) {
     extern __shared__ __attribute__((aligned(16))) float cl_lds[];
@@ -184,6 +193,7 @@ __global__ __launch_bounds__(256) void clip_attention_kernel(const float *__rest
     for (int r0 = 0; r0 < T; r0 += 4) {
         const int row = r0 + w;
         const bool ok = row < T;                              // wave-uniform
+        const int lim = CAUSAL ? row + 1 : T;                 // the keys this row sees: [0, lim), wave-uniform
         if (ok) {
             float4 q[D / 4];
 #pragma unroll
@@ -193,7 +203,7 @@ __global__ __launch_bounds__(256) void clip_attention_kernel(const float *__rest
             for (int j = 0; j < CL_KEYS; j++) {
                 const int k = lane + 64 * j;
                 s[j] = -INFINITY;
-                if (k < T) {
+                if (k < lim) {
                     const float *kr = Ks + k * KS;
                     float a = 0.f;
 #pragma unroll
@@ -211,18 +221,18 @@ __global__ __launch_bounds__(256) void clip_attention_kernel(const float *__rest
             float den = 0.f;
 #pragma unroll
             for (int j = 0; j < CL_KEYS; j++) {
-                s[j] = lane + 64 * j < T ? expf(s[j] - mx) : 0.f;
+                s[j] = lane + 64 * j < lim ? expf(s[j] - mx) : 0.f;
                 den += s[j];
             }
             den = wave_sum(den);
 #pragma unroll
             for (int j = 0; j < CL_KEYS; j++)
-                if (lane + 64 * j < T) pw[lane + 64 * j] = s[j] / den;
+                if (lane + 64 * j < lim) pw[lane + 64 * j] = s[j] / den;
         }
         __syncthreads();
         if (ok && lane < D) {
             float o = 0.f;
-            for (int k = 0; k < T; k++) o = fmaf(pw[k], Vs[k * D + lane], o);
+            for (int k = 0; k < lim; k++) o = fmaf(pw[k], Vs[k * D + lane], o);
             out[((int64_t)n * T + row) * Wd + h * D + lane] = o;
         }
         __syncthreads();
@@ -230,12 +240,47 @@ __global__ __launch_bounds__(256) void clip_attention_kernel(const float *__rest
 }
 
 // The 160 KB limit is raised once per kernel variant and device: the flags of RICK_LDS160_ONCE belong to its expansion site,
-// and this function template is one expansion site per D.
-template <int D>
+// and this function template is one expansion site per (D, CAUSAL).
+template <int D, bool CAUSAL>
 static void cl_attention_launch(const float *qkv, float *out, int N, int T, int Wd, int heads, hipStream_t st) {
     const size_t lds = cl_attention_lds(T, D);
-    if (lds > 64 * 1024) RICK_LDS160_ONCE(clip_attention_kernel<D>);
-    hipLaunchKernelGGL(clip_attention_kernel<D>, dim3((unsigned)(N * heads)), dim3(256), lds, st, qkv, out, T, Wd, heads);
+    if (lds > 64 * 1024) RICK_LDS160_ONCE((clip_attention_kernel<D, CAUSAL>));
+    hipLaunchKernelGGL((clip_attention_kernel<D, CAUSAL>), dim3((unsigned)(N * heads)), dim3(256), lds, st, qkv, out, T, Wd, heads);
+}
+
+// ---- the text tower's two row kernels ---------------------------------------------------------------------------------------------
+// out[n, t, :] = table[ids[n, t]] + pos[t]: one thread per four columns, one fp32 add per element, 16-byte accesses.  The host
+// validates the ids before upload; the kernel still forces an id into [0, V) so that no launch reads outside the table.
+__global__ __launch_bounds__(256) void clip_text_tokens_kernel(const int *__restrict__ ids, const float *__restrict__ table,
+                                                               const float *__restrict__ pos, float *__restrict__ out, int64_t total,
+                                                               int T, int V, int C4) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;                // over [N T][C / 4]
+    if (i >= total) return;
+    const int64_t row = i / C4;
+    const int c = (int)(i % C4), t = (int)(row % T);
+    const int id = min(max(ids[row], 0), V - 1);
+    const float4 a = reinterpret_cast<const float4 *>(table)[(int64_t)id * C4 + c];
+    const float4 d = reinterpret_cast<const float4 *>(pos)[(int64_t)t * C4 + c];
+    reinterpret_cast<float4 *>(out)[i] = make_float4(a.x + d.x, a.y + d.y, a.z + d.z, a.w + d.w);
+}
+
+// LayerNorm of the rows idx[r] of in (rows of C floats, compact) -> out [R, C]: clip_layernorm_kernel with the row number read
+// from idx, the same loads into the same registers and the same cl_layernorm_row, so the same bits as that kernel on the rows
+// gathered contiguously.  Neither the entry (idx is device memory, and there is no row count) nor the kernel can bound an index
+// from above: the host checks idx against the rows of `in` before upload, and an index past them reads out of bounds.
+__global__ __launch_bounds__(256) void clip_layernorm_rows_kernel(const float *__restrict__ in, const int *__restrict__ idx,
+                                                                  const float *__restrict__ w, const float *__restrict__ b,
+                                                                  float *__restrict__ out, int R, int C, float eps) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (row >= R) return;                                     // wave-uniform
+    const float *p = in + (int64_t)max(idx[row], 0) * C;
+    float4 x[CL_MAXJ];
+#pragma unroll
+    for (int j = 0; j < CL_MAXJ; j++) {
+        const int c = 4 * lane + 256 * j;
+        x[j] = c < C ? *reinterpret_cast<const float4 *>(p + c) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    cl_layernorm_row(x, C, lane, w, b, eps, out + (int64_t)row * C);
 }
 
 // ---- QuickGELU as a kernel of its own, and its derivative -----------------------------------------------------------------------
@@ -649,7 +694,8 @@ extern "C" int rick_clip_tokens_f32(const float *patches, const float *cls, cons
     RICK_LAUNCH_STATUS();
 }
 
-extern "C" int rick_clip_attention_f32(const float *qkv, float *out, int N, int T, int heads, int D, void *stream) {
+template <bool CAUSAL>
+static int cl_attention_entry(const float *qkv, float *out, int N, int T, int heads, int D, void *stream) {
     if (!qkv || !out || N < 0 || T < 1 || T > CL_MAXT || heads < 1 || heads > 1024 || (D != 16 && D != 32 && D != 64) ||
         !cl_aligned16(qkv, out))
         return RICK_EINVAL;
@@ -657,10 +703,42 @@ extern "C" int rick_clip_attention_f32(const float *qkv, float *out, int N, int 
     if ((int64_t)N * heads > 0x7fffffff || cl_attention_lds(T, D) > 160 * 1024) return RICK_EINVAL;
     const int Wd = heads * D;
     hipStream_t st = (hipStream_t)stream;
-    if (D == 16) cl_attention_launch<16>(qkv, out, N, T, Wd, heads, st);
-    else if (D == 32) cl_attention_launch<32>(qkv, out, N, T, Wd, heads, st);
-    else cl_attention_launch<64>(qkv, out, N, T, Wd, heads, st);
+    if (D == 16) cl_attention_launch<16, CAUSAL>(qkv, out, N, T, Wd, heads, st);
+    else if (D == 32) cl_attention_launch<32, CAUSAL>(qkv, out, N, T, Wd, heads, st);
+    else cl_attention_launch<64, CAUSAL>(qkv, out, N, T, Wd, heads, st);
     RICK_LAUNCH_STATUS();
+}
+
+extern "C" int rick_clip_text_tokens_f32(const int32_t *ids, const float *table, const float *pos, float *out, int N, int T, int V,
+                                         int C, void *stream) {
+    if (!ids || !table || !pos || !out || N < 0 || T < 1 || T > CL_MAXT || V < 1 || C <= 0 || (C & 3) || C > CL_MAXC ||
+        ((uintptr_t)ids & 3) || !cl_aligned16(table, pos, out))
+        return RICK_EINVAL;
+    if (N == 0) return 0;
+    const int64_t total = (int64_t)N * T * (C / 4);
+    if (cdiv64(total, 256) > 0x7fffffff) return RICK_EINVAL;                  // the grid's x extent
+    hipLaunchKernelGGL(clip_text_tokens_kernel, dim3((unsigned)cdiv64(total, 256)), dim3(256), 0, (hipStream_t)stream, ids, table, pos,
+                       out, total, T, V, C / 4);
+    RICK_LAUNCH_STATUS();
+}
+
+extern "C" int rick_clip_layernorm_rows_f32(const float *in, const int32_t *idx, const float *w, const float *b, float *out, int R,
+                                            int C, float eps, void *stream) {
+    if (!in || !idx || !w || !b || !out || R < 0 || C <= 0 || (C & 3) || C > CL_MAXC || !(eps >= 0.f) || ((uintptr_t)idx & 3) ||
+        !cl_aligned16(in, w, b, out))
+        return RICK_EINVAL;
+    if (R == 0) return 0;
+    hipLaunchKernelGGL(clip_layernorm_rows_kernel, dim3((unsigned)cdiv(R, 4)), dim3(256), 0, (hipStream_t)stream, in, idx, w, b, out, R,
+                       C, eps);
+    RICK_LAUNCH_STATUS();
+}
+
+extern "C" int rick_clip_attention_f32(const float *qkv, float *out, int N, int T, int heads, int D, void *stream) {
+    return cl_attention_entry<false>(qkv, out, N, T, heads, D, stream);
+}
+
+extern "C" int rick_clip_attention_causal_f32(const float *qkv, float *out, int N, int T, int heads, int D, void *stream) {
+    return cl_attention_entry<true>(qkv, out, N, T, heads, D, stream);
 }
 
 extern "C" int rick_clip_quickgelu_f32(const float *u, float *out, int64_t n, void *stream) {

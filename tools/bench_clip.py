@@ -7,6 +7,9 @@ tensors).  Seeded synthetic weights (timing only).
   python tools/bench_clip.py [--iters 20] [--rounds 5]
   python tools/bench_clip.py --backward      forward + backward of ClipImageFeatures.encode at n = 4, 8 and 25 against the fp32
                                              torch autograd composition on the same GPU, and the backward pass per kernel family
+  python tools/bench_clip.py --text          the text tower (rick_amd/cliptext.py): prompts/s for 160 prompts of 77 tokens at the
+                                             ViT-B/32 text dimensions (width 512, 8 heads, 12 layers, vocab 49408, random
+                                             weights), beside rick_amd.cliptext.torch_text_forward on the same CUDA tensors
 The two implementations are timed alternately, `--rounds` times each after a warm-up of both; the report gives the median
 and every round.  Prints a readable report and one JSON line."""
 import argparse
@@ -21,6 +24,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 VIT_B32 = dict(width=768, patch=32, image=224, layers=12, mlp=3072, dim=512)
+VIT_B32_TEXT = dict(width=512, tokens=77, vocab=49408, layers=12, mlp=2048, dim=512)       # 8 heads
 
 
 def timed(fn, iters):
@@ -184,15 +188,49 @@ def main_backward(args):
     print(json.dumps(res))
 
 
+def main_text(args):
+    """160 prompts of 77 tokens through ClipTextFeatures at the ViT-B/32 text dimensions, against torch_text_forward on the
+    same CUDA tensors."""
+    from rick_amd.cliptext import ClipTextFeatures, params_from_state_dict, torch_text_forward
+    from tests.cliptext_f64 import synthetic_text_state_dict, text_prompts
+    torch.backends.cudnn.allow_tf32 = False
+    torch.backends.cuda.matmul.allow_tf32 = False
+    dev, n = 'cuda', 160
+    params = params_from_state_dict(synthetic_text_state_dict(VIT_B32_TEXT, 0))
+    pd = {k: v.to(dev) for k, v in params.items()}
+    net = ClipTextFeatures(params, device=dev, batch=n, heads=8)
+    cfg = net.cfg
+    ids = text_prompts(n, cfg.tokens, cfg.vocab, seed=n).to(dev)
+    hip = lambda: net(ids)                                                    # noqa: E731  (validates on the host and uploads, as a user's call does)
+    with torch.no_grad():
+        ref = lambda: torch_text_forward(pd, cfg, ids)                        # noqa: E731
+        diff = float((hip() - ref()).abs().max() / ref().abs().max())
+        timed(hip, 3), timed(ref, 3)                                          # warm-up of both
+        th, tt = [], []
+        for _ in range(args.rounds):
+            th.append(timed(hip, args.iters))
+            tt.append(timed(ref, args.iters))
+    h, t = sorted(th)[len(th) // 2], sorted(tt)[len(tt) // 2]
+    res = {'metric': 'clip_vit_b32_text', 'hip_prompts_s': n / h, 'torch_prompts_s': n / t, 'hip_ms': h * 1e3, 'torch_ms': t * 1e3,
+           'max_rel_diff_vs_torch': diff}
+    print(f'ViT-B/32 text tower, {n} prompts of {cfg.tokens} tokens: HIP kernels {n / h:8.1f} prompts/s ({h * 1e3:.2f} ms)   torch fp32 '
+          f'composition {n / t:8.1f} prompts/s ({t * 1e3:.2f} ms)   hip / torch = {h / t:.3f}   max rel diff {diff:.2e}')
+    print('    rounds (ms)  hip: ' + ' '.join(f'{v * 1e3:.2f}' for v in th) + '   torch: ' + ' '.join(f'{v * 1e3:.2f}' for v in tt))
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--iters', type=int, default=20, help='passes per timed round')
     ap.add_argument('--rounds', type=int, default=5)
     ap.add_argument('--backward', action='store_true', help='time forward + backward of encode instead')
+    ap.add_argument('--text', action='store_true', help='time the text tower (rick_amd/cliptext.py) instead')
     ap.add_argument('--n', type=int, nargs='+', default=[4, 8, 25], help='batch sizes of --backward')
     args = ap.parse_args()
     if args.backward:
         return main_backward(args)
+    if args.text:
+        return main_text(args)
     from rick_amd.clip import ClipImageFeatures, params_from_state_dict, torch_forward
     from tests.clip_f64 import synthetic_clip_state_dict
     torch.backends.cudnn.allow_tf32 = False

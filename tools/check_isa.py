@@ -28,7 +28,7 @@ NO_PACKING = {'modulation.hip': ['modbank_fwd_kernel'], 'linear.hip': ['linear_f
               'lpips.hip': ['lp_invnorm_kernel', 'lp_pair_kernel'], 'gram.hip': ['gram_kernel', 'xgram_kernel'],
               'kml.hip': ['kml_grad_kernel'], 'svd.hip': ['svd_grad_kernel'], 'patchd.hip': ['patch_head_fwd_kernel'],
               'clip.hip': ['clip_layernorm_kernel', 'clip_tokens_kernel', 'clip_attention_kernel', 'clip_layernorm_bwd_kernel',
-                           'clip_tokens_bwd_kernel', 'clip_attention_bwd_q_kernel', 'clip_attention_bwd_kv_kernel']}
+                           'clip_tokens_bwd_kernel', 'clip_attention_bwd_q_kernel', 'clip_attention_bwd_kv_kernel', 'clip_layernorm_rows_kernel']}
 
 
 PER_FILE = {'linear.hip': ['-fno-slp-vectorize'], 'lpips.hip': ['-fno-slp-vectorize'], 'gram.hip': ['-fno-slp-vectorize'],
