@@ -1,5 +1,6 @@
-"""What the evaluation networks (rick_amd/inception.py, vgg.py, lpips.py) share around their kernels: reading a state_dict,
-checking an image batch, naming the device.  `who` is the class the error message names."""
+"""What the evaluation networks (rick_amd/inception.py, vgg.py, lpips.py) and the two CLIP towers (clip.py, cliptext.py, through
+cliptower.py) share around their kernels: reading a state_dict, checking an image batch, naming the device.  `who` is the
+class the error message names."""
 import torch
 
 

@@ -39,49 +39,33 @@ def timed(fn, iters):
     return e0.elapsed_time(e1) / 1e3 / iters
 
 
+def pick(launches, *what):
+    """A function that issues those of a pass's resolved launches (rick_amd/cliptower.py) whose place in it is one of `what`."""
+    from rick_amd.cliptower import issue
+    chosen = [s for s in launches if s.what in what]
+    assert chosen, what
+    return lambda: issue(chosen)
+
+
 def families(net, n, x):
     """{family: a function that issues that family's launches of one forward pass of n images}, on the plan's buffers."""
     from rick_amd import _lib as L
-    from rick_amd.clip import EPS
-    from rick_amd.fc import run_fc
-    plan, c, lib = net._plan, net.cfg, L.lib
-    d, v, rows = plan._descriptors(n), plan.vec, n * c.tokens
+    plan, c = net._plan, net.cfg
     out = torch.empty(n, c.dim, device=x.device)
-
-    def gemm(name, src, res=None, act=0):
-        wpk, bias, _, _ = plan.gemm[name]
-        L.check(lib.rick_inc_conv_lin_f32(src.data_ptr(), wpk.data_ptr(), bias.data_ptr(), None if res is None else res.data_ptr(), act,
-                                          d[name], L.stream_ptr()), 'rick_inc_conv_lin_f32')
-
-    def layernorm(name, src, ldx, dst, r):
-        L.check(lib.rick_clip_layernorm_f32(src.data_ptr(), ldx, v[name + '.w'].data_ptr(), v[name + '.b'].data_ptr(), dst.data_ptr(), r,
-                                            c.width, EPS, L.stream_ptr()), 'rick_clip_layernorm_f32')
-
-    def each_layer(fn):
-        return lambda: [fn(f'blocks.{i}.') for i in range(c.layers)]
-
-    def layernorms():
-        for i in range(c.layers):
-            layernorm(f'blocks.{i}.ln1', plan.tok, c.width, plan.ln, rows)
-            layernorm(f'blocks.{i}.ln2', plan.tok, c.width, plan.ln, rows)
-        layernorm('ln_post', plan.tok, c.tokens * c.width, plan.post, n)
-
+    net(x)                                                                    # the launches of n images are resolved
+    fwd = plan.fwd[n]
     return {
-        'input (bicubic + affine)': lambda: L.check(lib.rick_clip_input_f32(x.data_ptr(), plan.x0.data_ptr(), n, x.shape[2], x.shape[3],
-                                                                            c.size, L.stream_ptr()), 'rick_clip_input_f32'),
-        'patch embedding GEMM': lambda: gemm('patch', plan.x0),
-        'tokens + ln_pre': lambda: L.check(lib.rick_clip_tokens_f32(plan.patches.data_ptr(), v['cls'].data_ptr(), v['pos'].data_ptr(),
-                                                                    v['ln_pre.w'].data_ptr(), v['ln_pre.b'].data_ptr(), plan.tok.data_ptr(),
-                                                                    n, c.tokens, c.width, EPS, L.stream_ptr()), 'rick_clip_tokens_f32'),
-        'LayerNorm (2 per layer + ln_post)': layernorms,
-        'q/k/v GEMM': each_layer(lambda b: gemm(b + 'qkv', plan.ln)),
-        'attention': each_layer(lambda b: L.check(lib.rick_clip_attention_f32(plan.qkv.data_ptr(), plan.att.data_ptr(), n, c.tokens, c.heads,
-                                                                              c.width // c.heads, L.stream_ptr()), 'rick_clip_attention_f32')),
-        'out_proj GEMM + residual': each_layer(lambda b: gemm(b + 'out', plan.att, res=plan.tok)),
-        'c_fc GEMM + QuickGELU': each_layer(lambda b: gemm(b + 'fc', plan.ln, act=1)),
-        'c_proj GEMM + residual': each_layer(lambda b: gemm(b + 'proj', plan.hid, res=plan.tok)),
-        'projection (rick_fc_f32)': lambda: run_fc(plan.post.data_ptr(), plan.head.data_ptr(), plan.head_bias.data_ptr(), plan.ws.data_ptr(),
-                                                   out.data_ptr(), n, c.width, c.dim, 0),
+        'input (bicubic + affine)': lambda: L.check(L.lib.rick_clip_input_f32(x.data_ptr(), plan.x0.data_ptr(), n, x.shape[2], x.shape[3],
+                                                                              c.size, L.stream_ptr()), 'rick_clip_input_f32'),
+        'patch embedding GEMM': pick(fwd, 'patch'),
+        'tokens + ln_pre': pick(fwd, 'tokens'),
+        'LayerNorm (2 per layer + ln_post)': pick(fwd, 'ln1', 'ln2', 'ln_post'),
+        'q/k/v GEMM': pick(fwd, 'qkv'),
+        'attention': pick(fwd, 'attention'),
+        'out_proj GEMM + residual': pick(fwd, 'out'),
+        'c_fc GEMM + QuickGELU': pick(fwd, 'fc'),
+        'c_proj GEMM + residual': pick(fwd, 'proj'),
+        'projection (rick_fc_f32)': lambda: plan.tf.project(n, out),
     }
 
 
@@ -89,45 +73,23 @@ def backward_families(net, n):
     """{family: a function that issues that family's launches of one backward pass of n images}, on the gradient workspace's
     buffers after a differentiable forward run."""
     from rick_amd import _lib as L
-    from rick_amd.clip import EPS
     from rick_amd.fc import run_fc
-    ws, c, lib = net._grad_workspace(), net.cfg, L.lib
-    d, v, rows, wd = ws._descriptors(n), net._plan.vec, n * c.tokens, c.width
+    ws, c = net._grad_workspace(), net.cfg
+    bwd = ws.backward_launches(n)
     gx, go = torch.empty(n, 3, 256, 256, device=ws.gt.device), torch.ones(n, c.dim, device=ws.gt.device)
-
-    def ln_bwd(name, x, ldx, g, add, ld, r):
-        L.check(lib.rick_clip_layernorm_bwd_f32(x.data_ptr(), ldx, v[name + '.w'].data_ptr(), g.data_ptr(), wd,
-                                                None if add is None else add.data_ptr(), ws.gt.data_ptr(), ld, r, wd, EPS, L.stream_ptr()),
-                'rick_clip_layernorm_bwd_f32')
-
-    def layernorms():
-        ln_bwd('ln_post', ws.res[-1], c.tokens * wd, ws.gpost, None, c.tokens * wd, n)
-        for i in range(c.layers):
-            ln_bwd(f'blocks.{i}.ln2', ws.res[2 * i + 1], wd, ws.ga, ws.gt, wd, rows)
-            ln_bwd(f'blocks.{i}.ln1', ws.res[2 * i], wd, ws.ga, ws.gt, wd, rows)
-
-    def each_layer(fn):
-        return lambda: [fn(i, f'blocks.{i}.') for i in range(c.layers)]
-
-    gemm = lambda name, src: ws._gemm(ws.gemm[name], d['b', name], src)        # noqa: E731
     return {
         'projection^T (rick_fc_f32)': lambda: run_fc(go.data_ptr(), ws.head_t.data_ptr(), ws.head_t_bias.data_ptr(), ws.ws.data_ptr(),
-                                                     ws.gpost.data_ptr(), n, c.dim, wd, 0),
-        'LayerNorm backward (2 per layer + ln_post)': layernorms,
-        'c_proj^T GEMM': each_layer(lambda i, b: gemm(b + 'proj', ws.gt)),
-        'QuickGELU derivative': each_layer(lambda i, b: L.check(lib.rick_clip_quickgelu_bwd_f32(
-            ws.pre[i].data_ptr(), ws.gh.data_ptr(), ws.gh.data_ptr(), rows * c.mlp, L.stream_ptr()), 'rick_clip_quickgelu_bwd_f32')),
-        'c_fc^T GEMM': each_layer(lambda i, b: gemm(b + 'fc', ws.gh)),
-        'out_proj^T GEMM': each_layer(lambda i, b: gemm(b + 'out', ws.gt)),
-        'attention backward (2 launches)': each_layer(lambda i, b: L.check(lib.rick_clip_attention_bwd_f32(
-            ws.qkv[i].data_ptr(), ws.ga.data_ptr(), ws.stats.data_ptr(), ws.gq.data_ptr(), n, c.tokens, c.heads, wd // c.heads,
-            L.stream_ptr()), 'rick_clip_attention_bwd_f32')),
-        'q/k/v^T GEMM (K = 3 Wd)': each_layer(lambda i, b: gemm(b + 'qkv', ws.gq)),
-        'tokens + ln_pre adjoint': lambda: L.check(lib.rick_clip_tokens_bwd_f32(
-            ws.patches.data_ptr(), v['pos'].data_ptr(), v['ln_pre.w'].data_ptr(), ws.gt.data_ptr(), ws.gp.data_ptr(), n, c.tokens, wd, EPS,
-            L.stream_ptr()), 'rick_clip_tokens_bwd_f32'),
-        'patch embedding^T GEMM': lambda: gemm('patch', ws.gp),
-        'input adjoint (bicubic + affine)': lambda: L.check(lib.rick_clip_input_bwd_f32(
+                                                     ws.gpost.data_ptr(), n, c.dim, c.width, 0),
+        'LayerNorm backward (2 per layer + ln_post)': pick(bwd, 'ln_bwd'),
+        'c_proj^T GEMM': pick(bwd, 'proj^T'),
+        'QuickGELU derivative': pick(bwd, 'quickgelu_bwd'),
+        'c_fc^T GEMM': pick(bwd, 'fc^T'),
+        'out_proj^T GEMM': pick(bwd, 'out^T'),
+        'attention backward (2 launches)': pick(bwd, 'attention_bwd'),
+        'q/k/v^T GEMM (K = 3 Wd)': pick(bwd, 'qkv^T'),
+        'tokens + ln_pre adjoint': pick(bwd, 'tokens_bwd'),
+        'patch embedding^T GEMM': pick(bwd, 'patch^T'),
+        'input adjoint (bicubic + affine)': lambda: L.check(L.lib.rick_clip_input_bwd_f32(
             ws.gx0.data_ptr(), gx.data_ptr(), n, 256, 256, c.size, c.patch, L.stream_ptr()), 'rick_clip_input_bwd_f32'),
     }
 
