@@ -21,6 +21,7 @@ from . import op
 from ._lib import check, lib, ptr, stream_ptr
 from . import augment as A
 from . import diffaug as DA
+from . import gterms
 from .augment import augment_fused
 from .diffaug import diffaug_fused
 from .flat import FLAT_ALIGN, FisherAccumulator, FlatParams, MaskedFlatAdam, ema_flat  # noqa: F401  (re-exported)
@@ -327,30 +328,20 @@ def d_optim_filter(name):
 
 class RickTrainer:
     """One process / one GPU worth of the adaptation loop.  `dp` (rick_amd.dist.DataParallelGrads
-    or None) averages flat gradients over ranks with RCCL before each optimiser step.  `g_source`: the frozen source
-    generator of the distance-consistency term and of the dual contrastive terms (required when cfg.cdc_weight, cfg.dcl_g_weight
-    or cfg.dcl_d_weight > 0; put in eval mode, gradients off); `d_source`: the frozen source discriminator of the discriminator
-    contrastive term (required when cfg.dcl_d_weight > 0; treated like g_source).  `ewc`: the
+    or None) averages flat gradients over ranks with RCCL before each optimiser step.  The G step's extra loss terms are
+    rick_amd/gterms.py's (`g_terms`: the ones switched on; each checks its own configuration and resources).  `g_source`: the
+    frozen source generator those terms and the discriminator contrastive term need (put in eval mode, gradients off);
+    `d_source`: the frozen source discriminator of the discriminator contrastive term (required with g_source when
+    cfg.dcl_d_weight > 0; treated like g_source).  `ewc`: the
     anchor of the elastic-weight-consolidation term (required when cfg.ewc_weight > 0), given as what `set_ewc` takes: a pair
     (source_state, fisher) of {name: tensor} mappings, fisher None for the L2-SP penalty.  `patch_heads`: the
     rick_amd.patchd.PatchHeads of CDC's patch-level discriminator (cfg.subspace_freq > 0; built here when None).  Deviation from
     CDC as recalled: R1 stays on the image-level logits, where CDC sends it through the patch head on patch iterations.
-    `clip`: the rick_amd.clipguide.ClipGuide (encoder and direction) of the CLIP-space terms, required with g_source when
-    cfg.clip_dir_weight or cfg.clip_within_weight > 0; with both at 0 it is never used."""
+    `clip`: the rick_amd.clipguide.ClipGuide (encoder and direction) of the CLIP-space terms; never used while they are off."""
 
     def __init__(self, cfg, generator, discriminator, g_ema, d_ema, dp=None, g_source=None, ewc=None, d_source=None,
                  patch_heads=None, clip=None):
         self.cfg, self.g, self.d, self.g_ema, self.d_ema, self.dp = cfg, generator, discriminator, g_ema, d_ema, dp
-        for w in (cfg.clip_dir_weight, cfg.clip_within_weight):
-            if w < 0 or not math.isfinite(w):
-                raise ValueError('RickTrainer: clip_dir_weight and clip_within_weight must be finite and >= 0')
-        self.clip = clip
-        if cfg.clip_dir_weight > 0 or cfg.clip_within_weight > 0:
-            if g_source is None or clip is None:
-                raise ValueError('RickTrainer: clip_dir_weight / clip_within_weight > 0 need the frozen source generator and the '
-                                 'CLIP guide (g_source=, clip=ClipGuide(net, direction))')
-            if cfg.clip_batch < (2 if cfg.clip_within_weight > 0 else 1):
-                raise ValueError('RickTrainer: clip_batch must be >= 1, and >= 2 with clip_within_weight > 0')
         # the discriminator-side augmentation: DiffAugment (cfg.diffaug) or ADA (cfg.augment), never both; None when both are off
         self._augmenter = AdaAugmenter(self) if cfg.augment else None
         if cfg.diffaug:
@@ -358,15 +349,11 @@ class RickTrainer:
             if cfg.augment:
                 raise ValueError('RickTrainer: augment (ADA) and diffaug are alternatives; set one of them')
         self.device = next(generator.parameters()).device
-        self.g_source, self.d_source = g_source, d_source
-        if cfg.cdc_weight < 0 or (cfg.cdc_weight > 0 and cfg.cdc_batch < 2):
-            raise ValueError('RickTrainer: cdc_weight must be >= 0 and cdc_batch >= 2')
+        self.g_source, self.d_source, self.clip = g_source, d_source, clip
         if cfg.ewc_weight < 0 or not math.isfinite(cfg.ewc_weight):
             raise ValueError('RickTrainer: ewc_weight must be finite and >= 0')
         if cfg.ewc_weight > 0 and ewc is None:
             raise ValueError('RickTrainer: ewc_weight > 0 needs the anchor (ewc=(source_state, fisher))')
-        if cfg.cdc_weight > 0 and g_source is None:
-            raise ValueError('RickTrainer: cdc_weight > 0 needs the frozen source generator (g_source=)')
         if isinstance(cfg.kml_rank, bool) or not isinstance(cfg.kml_rank, int) or not 0 <= cfg.kml_rank <= 8:
             raise ValueError('RickTrainer: kml_rank must be an integer in 0 ... 8')
         if cfg.svd_adapt and cfg.kml_rank > 0:
@@ -374,13 +361,10 @@ class RickTrainer:
         if cfg.svd_adapt and cfg.warmup_iter > 0:
             raise ValueError('RickTrainer: svd_adapt needs warmup_iter = 0 (the warm-up stage switches D\'s gradients off layer by '
                              'layer; singular-value adaptation has no such stage)')
-        for w in (cfg.dcl_g_weight, cfg.dcl_d_weight):
-            if w < 0 or not math.isfinite(w):
-                raise ValueError('RickTrainer: dcl_g_weight and dcl_d_weight must be finite and >= 0')
-        if not cfg.dcl_tau > 0 or not math.isfinite(cfg.dcl_tau) or cfg.dcl_batch < 1:
-            raise ValueError('RickTrainer: dcl_tau must be > 0 and dcl_batch >= 1')
-        if cfg.dcl_g_weight > 0 and g_source is None:
-            raise ValueError('RickTrainer: dcl_g_weight > 0 needs the frozen source generator (g_source=)')
+        if cfg.dcl_d_weight < 0 or not math.isfinite(cfg.dcl_d_weight):
+            raise ValueError('RickTrainer: dcl_d_weight must be finite and >= 0')
+        if not cfg.dcl_tau > 0 or not math.isfinite(cfg.dcl_tau):         # the temperature of both contrastive terms
+            raise ValueError('RickTrainer: dcl_tau must be finite and > 0')
         if cfg.dcl_d_weight > 0 and (g_source is None or d_source is None):
             raise ValueError('RickTrainer: dcl_d_weight > 0 needs the frozen source generator and discriminator (g_source=, d_source=)')
         if cfg.dcl_d_weight > 0 and (cfg.augment or cfg.diffaug):
@@ -396,6 +380,7 @@ class RickTrainer:
             src.eval()
             for p in src.parameters():
                 p.requires_grad = False
+        self.g_terms = gterms.build(self)       # the G step's extra loss terms that are on (rick_amd/gterms.py)
         if isinstance(cfg.subspace_freq, bool) or not isinstance(cfg.subspace_freq, int) or cfg.subspace_freq < 0:
             raise ValueError('RickTrainer: subspace_freq must be an integer >= 0')
         if cfg.subspace_freq > 0:
@@ -955,17 +940,6 @@ class RickTrainer:
         _, feats_t = self.g([z], noise=g_noise, return_feats=True)
         return feats_t, feats_s
 
-    def _cdc_term(self, cdc_noise=None, cdc_layers=None, g_noise=None):
-        """The unweighted distance-consistency loss (rick_amd/cdc.py) of one draw: z ~ N(0, I) [cdc_batch, latent] through the
-        frozen source generator (no grad) and the generator being trained, compared at one drawn feature layer per sample.
-        `g_noise`: fixed noise maps for both generators (drawn per call otherwise)."""
-        from . import cdc
-        cfg = self.cfg
-        z = cdc_noise if cdc_noise is not None else torch.randn(cfg.cdc_batch, cfg.latent, device=self.device)
-        layers = cdc_layers if cdc_layers is not None else cdc.draw_layers(self.g.n_latent, z.shape[0])
-        feats_t, feats_s = self._feature_pair(z, g_noise)
-        return cdc.distance_consistency_loss(feats_t, feats_s, layers)
-
     def _dcl_d_draws(self, noise, g_noise, inject=None):
         """The draws Generator.forward would make for the fakes of a D step, made here so that the generator being trained and the
         frozen source generator get the same ones: the style-mixing index (None for a single latent) and the noise maps."""
@@ -983,73 +957,21 @@ class RickTrainer:
                 o += B * r * r
         return inject, g_noise
 
-    def _dcl_g_term(self, dcl_noise=None, dcl_layers=None, g_noise=None, pair=None):
-        """The unweighted generator contrastive loss CL1 (rick_amd/dcl.py) of one draw: z ~ N(0, I) [dcl_batch, latent] through
-        the frozen source generator (no grad) and the generator being trained, one drawn feature layer per sample.  `pair`: a
-        forward pair (feats_t, feats_s) to use instead of making one (the distance-consistency term's, when the batches agree)."""
-        from . import cdc, dcl
-        cfg = self.cfg
-        if pair is None:
-            z = dcl_noise if dcl_noise is not None else torch.randn(cfg.dcl_batch, cfg.latent, device=self.device)
-            pair = self._feature_pair(z, g_noise)
-        feats_t, feats_s = pair
-        layers = dcl_layers if dcl_layers is not None else cdc.draw_layers(self.g.n_latent, feats_t[0].shape[0])
-        return dcl.generator_contrastive_loss(feats_t, feats_s, layers, cfg.dcl_tau)
-
-    def _consistency_terms(self, cdc_noise=None, cdc_layers=None, dcl_noise=None, dcl_layers=None, g_noise=None):
-        """The unweighted feature-consistency terms of a G step that are switched on, {'cdc': ..., 'dcl_g': ...}.  With both on and
-        equal batches they share ONE forward pair (the latents are cdc_noise, else dcl_noise, else drawn); otherwise each makes
-        its own."""
-        from . import cdc
-        cfg, out = self.cfg, {}
-        cdc_on, dcl_on = cfg.cdc_weight > 0, cfg.dcl_g_weight > 0
-        nc = cdc_noise.shape[0] if cdc_noise is not None else cfg.cdc_batch
-        nd = dcl_noise.shape[0] if dcl_noise is not None else cfg.dcl_batch
-        if cdc_on and dcl_on and nc == nd and (cdc_noise is None or dcl_noise is None or cdc_noise is dcl_noise):
-            z = cdc_noise if cdc_noise is not None else dcl_noise
-            if z is None:
-                z = torch.randn(nc, cfg.latent, device=self.device)
-            pair = self._feature_pair(z, g_noise)
-            layers = cdc_layers if cdc_layers is not None else cdc.draw_layers(self.g.n_latent, nc)
-            out['cdc'] = cdc.distance_consistency_loss(pair[0], pair[1], layers)
-            out['dcl_g'] = self._dcl_g_term(dcl_layers=dcl_layers, pair=pair)
-            return out
-        if cdc_on:
-            out['cdc'] = self._cdc_term(cdc_noise, cdc_layers, g_noise)
-        if dcl_on:
-            out['dcl_g'] = self._dcl_g_term(dcl_noise, dcl_layers, g_noise)
-        return out
-
-    def _clip_terms(self, clip_noise=None, g_noise=None):
-        """The unweighted CLIP-space terms (rick_amd/clipguide.py) of one draw: z ~ N(0, I) [clip_batch, latent] through the
-        frozen source generator (no grad) and through G with the same noise maps, both image batches through the encoder."""
-        cfg = self.cfg
-        z = clip_noise if clip_noise is not None else torch.randn(cfg.clip_batch, cfg.latent, device=self.device)
-        if g_noise is None:
-            g_noise = [n.expand(z.shape[0], -1, -1, -1).clone().normal_() for n in self.g.make_noise()]
-        with torch.no_grad():
-            fake_s, _ = self.g_source([z], noise=g_noise)
-        fake_t, _ = self.g([z], noise=g_noise)
-        return self.clip.terms(fake_t, fake_s, cfg.clip_dir_weight > 0, cfg.clip_within_weight > 0)
-
-    def g_step(self, noise, g_noise=None, graph=False, cdc_noise=None, cdc_layers=None, dcl_noise=None, dcl_layers=None,
-               patch=None, clip_noise=None):
-        """Non-saturating G step.  With cfg.cdc_weight > 0 the distance-consistency term is added before the one backward():
-        its drawn layers change the launch list from step to step, so such a step is never captured — `graph=True` then runs
-        the eager path (its own mixing noise, no step graph) while every other step type keeps replaying.  `cdc_noise`
-        [cdc_batch, latent] and `cdc_layers` fix the term's draws (tests); `g_noise` also fixes its noise maps.  The generator
-        contrastive term (cfg.dcl_g_weight > 0, `dcl_noise` / `dcl_layers`) is treated the same way, and so is every G step with
-        cfg.subspace_freq > 0 (rick_amd/patchd.py): `patch=p_ind` takes the non-saturating loss over the patch map of
-        patchd.patch_logits at that tap; neither the discriminator nor the heads get gradients.  The CLIP-space terms
-        (cfg.clip_dir_weight / cfg.clip_within_weight > 0, rick_amd/clipguide.py) are added the same way and also run eagerly;
-        `clip_noise` [clip_batch, latent] fixes their latents, `g_noise` their noise maps."""
-        cdc_on = self.cfg.cdc_weight > 0
-        clip_on = self.cfg.clip_dir_weight > 0 or self.cfg.clip_within_weight > 0
-        dcl_on = self.cfg.dcl_g_weight > 0
+    def g_step(self, noise, g_noise=None, graph=False, patch=None, **draws):
+        """Non-saturating G step.  The extra loss terms that are on (`g_terms`, rick_amd/gterms.py) are added before the one
+        backward(); `draws` are the keywords those terms declare to fix their random draws (tests), `g_noise` also fixes their
+        noise maps; a keyword of a term that is off is ignored, one that no term declares is a TypeError.  A term whose launch list
+        changes from step to step is not capturable: `graph=True` then runs the eager path (its own mixing noise, no step graph)
+        while every other step type keeps replaying, and so does every G step with cfg.subspace_freq > 0 (rick_amd/patchd.py):
+        `patch=p_ind` takes the non-saturating loss over the patch map of patchd.patch_logits at that tap; neither the
+        discriminator nor the heads get gradients."""
+        for k in draws:
+            if k not in gterms.DRAWS:
+                raise TypeError(f"RickTrainer.g_step() got an unexpected keyword argument '{k}'")
         patch_on = self.cfg.subspace_freq > 0
         if patch is not None and not patch_on:
             raise ValueError('RickTrainer.g_step: patch= needs cfg.subspace_freq > 0')
-        if (cdc_on or dcl_on or patch_on or clip_on) and graph:
+        if (patch_on or not all(t.capturable for t in self.g_terms)) and graph:
             graph = False
             if noise is None:
                 noise = mixing_noise(self.cfg.batch, self.cfg.latent, self.cfg.mixing, self.device)
@@ -1078,22 +1000,11 @@ class RickTrainer:
                     fake_pred, _ = self.d(fake)
                 g_loss = g_nonsaturating_loss(fake_pred)
                 total = g_loss
-                if cdc_on and not dcl_on:
-                    cdc_loss = self._cdc_term(cdc_noise, cdc_layers, g_noise)
-                    total = g_loss + self.cfg.cdc_weight * cdc_loss
-                    self.losses['cdc'] = cdc_loss.detach()
-                elif dcl_on:
-                    terms = self._consistency_terms(cdc_noise, cdc_layers, dcl_noise, dcl_layers, g_noise)
-                    for name, weight in (('cdc', self.cfg.cdc_weight), ('dcl_g', self.cfg.dcl_g_weight)):
-                        if name in terms:
-                            total = total + weight * terms[name]
-                            self.losses[name] = terms[name].detach()
-                if clip_on:
-                    terms = self._clip_terms(clip_noise, g_noise)
-                    for name, weight in (('clip_dir', self.cfg.clip_dir_weight), ('clip_within', self.cfg.clip_within_weight)):
-                        if name in terms:
-                            total = total + weight * terms[name]
-                            self.losses[name] = terms[name].detach()
+                memo = {}                        # what one term hands to a later one (a shared forward pair)
+                for term in self.g_terms:
+                    for name, (weight, value) in term(draws, g_noise, memo).items():
+                        total = total + weight * value
+                        self.losses[name] = value.detach()
                 self._zero_grad(self.g_flat)
                 with op.deferred_sums(), op.wgrad_overlap():
                     total.backward()

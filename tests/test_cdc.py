@@ -181,7 +181,8 @@ def test_trainer_term_equals_the_stand_alone_loss():
     tr.g.forward, src.forward = _stand_in(tr.g), _stand_in(src)
     z = torch.randn(4, 512, generator=torch.Generator().manual_seed(2))
     layers = [1, 3, 3, 5]
-    term = tr._cdc_term(z, layers)
+    (cdc_term,) = tr.g_terms                                   # the only term that is on (rick_amd/gterms.py)
+    term = cdc_term({'cdc_noise': z, 'cdc_layers': layers}, None, {})['cdc'][1]
     with torch.no_grad():
         ref = cdc.distance_consistency_loss(tr.g([z], return_feats=True)[1], src([z], return_feats=True)[1], layers)
     assert float(ref) > 0 and torch.equal(term.detach(), ref)
@@ -202,7 +203,7 @@ def test_trainer_term_equals_the_stand_alone_loss():
         return out
     tr.g.forward = recording
     np.random.seed(0)
-    term = tr._cdc_term()
+    term = cdc_term({}, None, {})['cdc'][1]
     layers = np.random.RandomState(0).randint(1, tr.g.n_latent - 1, 4)
     assert seen['z'].shape == (4, 512) and seen['z'].device == tr.device
     with torch.no_grad():

@@ -286,11 +286,20 @@ def _stood_in(**cfg):
     return tr, gs, t_calls, s_calls
 
 
+def _terms(tr, g_noise=None, **draws):
+    """The unweighted values of the trainer's G-step terms (rick_amd/gterms.py), evaluated the way g_step's loop does."""
+    memo, out = {}, {}
+    for term in tr.g_terms:
+        out.update({name: value for name, (_, value) in term(draws, g_noise, memo).items()})
+    assert not memo                                                              # what was handed on was taken
+    return out
+
+
 def test_cl1_term_uses_one_forward_pair_and_the_source_without_grad():
     tr, gs, t_calls, s_calls = _stood_in(dcl_g_weight=2.0, dcl_batch=4)
     z = torch.randn(4, 512, generator=torch.Generator().manual_seed(2))
     layers, maps = [1, 3, 3, 5], object()
-    term = tr._dcl_g_term(z, layers, maps)
+    term = _terms(tr, maps, dcl_noise=z, dcl_layers=layers)['dcl_g']
     assert len(t_calls) == 1 and len(s_calls) == 1
     assert t_calls[0][:2] == (True, maps) and s_calls[0][:2] == (False, maps) and t_calls[0][2] is z and s_calls[0][2] is z
     feats_t, feats_s = tr._feature_pair(z)
@@ -303,7 +312,7 @@ def test_cl1_term_uses_one_forward_pair_and_the_source_without_grad():
     # the draws when none are given: dcl_batch latents, layers from cdc.draw_layers
     del t_calls[:], s_calls[:]
     np.random.seed(0)
-    term = tr._dcl_g_term()
+    term = _terms(tr)['dcl_g']
     z = t_calls[0][2]
     assert z.shape == (4, 512) and s_calls[0][2] is z
     feats_t, feats_s = tr._feature_pair(z)
@@ -314,18 +323,57 @@ def test_cl1_term_uses_one_forward_pair_and_the_source_without_grad():
 def test_cdc_and_cl1_share_the_pair_when_their_batches_agree():
     tr, gs, t_calls, s_calls = _stood_in(dcl_g_weight=2.0, dcl_batch=4, cdc_weight=1000.0, cdc_batch=4)
     z = torch.randn(4, 512, generator=torch.Generator().manual_seed(2))
-    terms = tr._consistency_terms(cdc_noise=z, cdc_layers=[1, 3, 3, 5], dcl_layers=[2, 2, 4, 1])
+    terms = _terms(tr, cdc_noise=z, cdc_layers=[1, 3, 3, 5], dcl_layers=[2, 2, 4, 1])
     assert len(t_calls) == 1 and len(s_calls) == 1 and s_calls[0][0] is False
     feats_t, feats_s = tr._feature_pair(z)
     assert torch.equal(terms['cdc'].detach(), cdc.distance_consistency_loss(feats_t, feats_s, [1, 3, 3, 5]).detach())
     assert torch.equal(terms['dcl_g'].detach(), dcl.generator_contrastive_loss(feats_t, feats_s, [2, 2, 4, 1], 0.07).detach())
     del t_calls[:], s_calls[:]
-    terms = tr._consistency_terms()                                              # nothing given: one drawn z for both
+    terms = _terms(tr)                                              # nothing given: one drawn z for both
     assert len(t_calls) == 1 and len(s_calls) == 1 and set(terms) == {'cdc', 'dcl_g'}
     # batches that differ: each term makes its own pair
     tr, gs, t_calls, s_calls = _stood_in(dcl_g_weight=2.0, dcl_batch=3, cdc_weight=1000.0, cdc_batch=4)
-    terms = tr._consistency_terms()
+    terms = _terms(tr)
     assert sorted(c[2].shape[0] for c in t_calls) == [3, 4] and len(s_calls) == 2 and set(terms) == {'cdc', 'dcl_g'}
     # one term on: only its own
     tr, gs, t_calls, s_calls = _stood_in(dcl_g_weight=2.0, dcl_batch=4)
-    assert set(tr._consistency_terms()) == {'dcl_g'} and len(t_calls) == 1
+    assert set(_terms(tr)) == {'dcl_g'} and len(t_calls) == 1
+
+
+@pytest.mark.parametrize('dcl_batch', [3, 4])
+def test_both_terms_consume_their_draws_in_the_fixed_order(dcl_batch):
+    """No draws given, both terms on: the torch stream gives the distance-consistency term's latents first and then, when the
+    batches differ (no shared pair), CL1's; numpy's global stream gives the distance-consistency term's layers first, then
+    CL1's.  (The stand-ins draw no noise maps.)  Both values equal the losses on the draws replayed by hand in that order."""
+    seed = 5
+    tr, gs, t_calls, s_calls = _stood_in(dcl_g_weight=2.0, dcl_batch=dcl_batch, cdc_weight=1000.0, cdc_batch=4)
+    torch.manual_seed(seed)
+    np.random.seed(seed)
+    terms = _terms(tr)
+    shared = dcl_batch == 4
+    assert len(t_calls) == len(s_calls) == (1 if shared else 2)
+    torch.manual_seed(seed)
+    z_cdc = torch.randn(4, 512)
+    z_dcl = z_cdc if shared else torch.randn(dcl_batch, 512)
+    got_cdc, got_dcl = t_calls[0][2], t_calls[-1][2]                             # read back before the replay records more calls
+    assert torch.equal(got_cdc, z_cdc) and torch.equal(got_dcl, z_dcl)
+    assert all(t[2] is s[2] for t, s in zip(t_calls, s_calls))
+    rng = np.random.RandomState(seed)
+    layers_cdc = rng.randint(1, tr.g.n_latent - 1, 4)
+    layers_dcl = rng.randint(1, tr.g.n_latent - 1, dcl_batch)
+    with torch.no_grad():
+        want_cdc = cdc.distance_consistency_loss(*tr._feature_pair(got_cdc), layers_cdc)
+        want_dcl = dcl.generator_contrastive_loss(*tr._feature_pair(got_dcl), layers_dcl, tr.cfg.dcl_tau)
+    assert torch.equal(terms['cdc'].detach(), want_cdc) and torch.equal(terms['dcl_g'].detach(), want_dcl)
+    assert float(want_cdc) > 0 and float(want_dcl) > 0
+
+
+def test_g_step_refuses_a_keyword_no_term_declares():
+    from rick_amd import gterms
+    assert gterms.DRAWS == {'cdc_noise', 'cdc_layers', 'dcl_noise', 'dcl_layers', 'clip_noise'}
+    tr, gs, t_calls, s_calls = _stood_in(dcl_g_weight=2.0)
+    with pytest.raises(TypeError, match='bogus'):
+        tr.g_step(None, bogus=1)                                                 # before any work: these networks have no CPU path
+    with pytest.raises(TypeError, match='bogus'):
+        tr.g_step(None, cdc_noise=None, bogus=1)                                 # next to a declared keyword of a term that is off
+    assert not t_calls and not s_calls

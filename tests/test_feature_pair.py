@@ -1,5 +1,5 @@
-"""RickTrainer._feature_pair: the one source / target forward pair behind the distance-consistency term, factored out of
-_cdc_term so that a further feature-consistency term can share it.  Stand-in generators (the generator itself has no CPU path),
+"""RickTrainer._feature_pair: the one source / target forward pair behind the distance-consistency term, a method of its own
+so that a further feature-pair term (rick_amd/gterms.py) can share it.  Stand-in generators (the generator itself has no CPU path),
 built the way tests/test_cdc.py builds them."""
 import torch
 
@@ -61,7 +61,9 @@ def test_cdc_term_is_the_loss_on_the_pair():
     tr, src, t_calls, s_calls = _trainer()
     z = torch.randn(4, 512, generator=torch.Generator().manual_seed(2))
     layers = [1, 3, 3, 5]
-    term = tr._cdc_term(z, layers)
+    (cdc_term,) = tr.g_terms                                                   # the only term that is on (rick_amd/gterms.py)
+    weight, term = cdc_term({'cdc_noise': z, 'cdc_layers': layers}, None, {})['cdc']
+    assert weight == 1000.0
     assert len(t_calls) == 1 and len(s_calls) == 1                             # one forward pair per term
     feats_t, feats_s = tr._feature_pair(z)
     assert torch.equal(term.detach(), cdc.distance_consistency_loss(feats_t, feats_s, layers).detach())

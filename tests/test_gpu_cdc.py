@@ -313,8 +313,9 @@ def test_g_step_gradient_is_the_sum_of_both_terms():
     on.g_step(fx['noise'], fx['g_noise'], cdc_noise=fx['cdc_noise'], cdc_layers=fx['cdc_layers'])
     off.g_step(fx['noise'], fx['g_noise'])
     named = [(n, p) for n, p in ref.g.named_parameters() if g_optim_filter(n)]
-    term = torch.autograd.grad(ref._cdc_term(fx['cdc_noise'], fx['cdc_layers'], fx['g_noise']), [p for _, p in named],
-                               allow_unused=True)
+    (cdc_term,) = ref.g_terms                                  # the only term that is on (rick_amd/gterms.py)
+    _, value = cdc_term({k: fx[k] for k in cdc_term.draws}, fx['g_noise'], {})['cdc']
+    term = torch.autograd.grad(value, [p for _, p in named], allow_unused=True)
     g_on = {n: p.grad for n, p in on.g.named_parameters()}
     g_off = {n: p.grad for n, p in off.g.named_parameters()}
     moved = 0

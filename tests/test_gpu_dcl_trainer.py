@@ -85,7 +85,8 @@ def test_g_step_term_parameter_gradients_and_value():
     ps = [p for _, p in named]
     ft, fs = tr._feature_pair(fx['z'], fx['g_noise'])
     assert len(ft) == tr.g.n_latent - 1 and not any(f.requires_grad for f in fs)
-    term = tr._dcl_g_term(dcl_layers=layers, pair=(ft, fs))
+    (dcl_term,) = tr.g_terms                                   # the only term that is on (rick_amd/gterms.py)
+    _, term = dcl_term({'dcl_layers': layers}, None, {dcl_term: (ft, fs)})['dcl_g']     # on this pair, as if it were handed on
     gd = torch.autograd.grad(term, ps, retain_graph=True, allow_unused=True)
     g64 = torch.autograd.grad(cl1_composed(ft, fs, layers, torch.float64), ps, retain_graph=True, allow_unused=True)
     g32 = torch.autograd.grad(cl1_composed(ft, fs, layers, torch.float32), ps, allow_unused=True)
@@ -237,3 +238,67 @@ def test_zero_weights_change_nothing():
         pa, pb = _params(na), _params(nb)
         assert all(torch.equal(pa[n], pb[n]) for n in pa)
     assert torch.equal(with_src.losses['g'], without.losses['g']) and torch.equal(with_src.losses['d'], without.losses['d'])
+
+
+def test_g_step_with_every_term_on_is_the_sum_of_the_terms():
+    """All extra terms of the G step together (rick_amd/gterms.py): distance consistency and CL1 on one shared forward pair, then
+    both CLIP-space terms on the tiny image configuration A.  Every draw and noise map is pinned.  Wiring, by the rule and the
+    bound of tests/test_gpu_cdc.py::test_g_step_gradient_is_the_sum_of_both_terms: each optimiser-owned tensor of the flat
+    gradient equals the plain step's plus the sum of weight times each term's own gradient, within 1e-3 of the tensor's largest
+    wanted entry (the two sides add the same fp32 contributions in another order; a missing or doubled term is an error of
+    order one).  The weights make every term at least 1e-2 of the adversarial gradient on four tensors or more: measured, on all
+    20 tensors of convs.0 ... convs.3 the smallest of the four ratios lies between 3.1e-2 and 2.8e-1 (the distance-consistency
+    term 3.7e-2 ... 1.2, CL1 0.12 ... 4.4, clip_dir 3.1e-2 ... 8.2, clip_within 0.17 ... 4.0; no feature list reaches convs.5
+    and the drawn layers leave convs.4 out of the distance-consistency term), and the largest error of the 30 is 5.9e-6."""
+    from rick_amd.clipguide import ClipGuide
+    from rick_amd.train import RickTrainer, TrainConfig, g_optim_filter
+    from tests.test_gpu_clip import network
+    from tests.test_gpu_clip_grad import _guide_inputs
+    make = _build()
+    weights = dict(cdc_weight=2048.0, dcl_g_weight=64.0, clip_dir_weight=0.25, clip_within_weight=0.25)
+
+    def trainer(**w):
+        g, d = make(perturb=0.3)
+        g_ema, d_ema = make()
+        cfg = TrainConfig(size=32, batch=2, n_mlp=2, warmup_iter=0, cdc_batch=4, dcl_batch=4, clip_batch=2, **w)
+        return RickTrainer(cfg, g, d, g_ema, d_ema, g_source=make()[0], clip=ClipGuide(network('A'), _guide_inputs()[2]))
+    on, off, ref = trainer(**weights), trainer(), trainer(**weights)
+    assert [type(t).__name__ for t in on.g_terms] == ['CdcTerm', 'DclGTerm', 'ClipTerm'] and off.g_terms == []
+    gen = torch.Generator(DEV).manual_seed(7)
+    noise = [torch.randn(2, 512, device=DEV, generator=gen)]
+    g_noise = [torch.randn(n.shape, device=DEV, generator=gen) for n in on.g.make_noise()]
+    draws = dict(cdc_noise=torch.randn(4, 512, device=DEV, generator=gen), cdc_layers=[2, 4, 2, 1], dcl_layers=[1, 3, 3, 5],
+                 clip_noise=torch.randn(2, 512, device=DEV, generator=gen))
+    source_calls = []
+    on.g_source.register_forward_hook(lambda mod, args, out: source_calls.append(args[0][0].shape[0]))
+    on.g_step(noise, g_noise, **draws)
+    off.g_step(noise, g_noise)
+    assert source_calls == [4, 2]                                                # the shared pair, then the CLIP terms' images
+    names = ('cdc', 'dcl_g', 'clip_dir', 'clip_within')
+    assert all(n in on.losses and torch.isfinite(on.losses[n]) for n in names) and not any(n in off.losses for n in names)
+    named = [(n, p) for n, p in ref.g.named_parameters() if g_optim_filter(n)]
+    own = {}
+    for name in names:                      # one evaluation per loss: the CLIP encoder keeps the activations of one backward pass
+        memo, found = {}, {}
+        for term in ref.g_terms:
+            found.update(term(draws, g_noise, memo))
+        weight, value = found[name]
+        assert weight == weights[name + '_weight'] and torch.equal(value.detach(), on.losses[name])
+        own[name] = [None if t is None else weight * t
+                     for t in torch.autograd.grad(value, [p for _, p in named], allow_unused=True)]
+    g_on = {n: p.grad for n, p in on.g.named_parameters()}
+    g_off = {n: p.grad for n, p in off.g.named_parameters()}
+    moved = 0
+    for k, (n, _) in enumerate(named):
+        want = g_off[n].clone()
+        ratios = []
+        for name in names:
+            t = own[name][k]
+            if t is not None:
+                want += t
+            ratios.append(0.0 if t is None else float(t.abs().max() / g_off[n].abs().max()))
+        err = float((g_on[n] - want).abs().max()) / float(want.abs().max())
+        print(f'{n}: err {err:.3e}; term / adversarial gradient ' + ', '.join(f'{a} {r:.3e}' for a, r in zip(names, ratios)))
+        assert err <= 1e-3, n
+        moved += min(ratios) > 1e-2
+    assert moved >= 4                                                            # every term is a visible part of the gradient
