@@ -1,5 +1,5 @@
 """What the kernel-forms tests share (test_gpu_wgrad_forms.py, test_gpu_igemm_forms.py, test_gpu_convt2_forms.py,
-test_gpu_ufd_forms.py, test_gpu_mod_forms.py, test_gpu_state_forms.py): guarded and fenced device buffers, the integer / 12-bit / scale generators of the exact modes, split images, the saturation counter, the
+test_gpu_ufd_forms.py, test_gpu_mod_forms.py, test_gpu_state_forms.py, test_gpu_gemm_forms.py, test_gpu_ada_forms.py): guarded and fenced device buffers, the integer / 12-bit / scale generators of the exact modes, split images, the saturation counter, the
 NaN-fence and amax-word checks, the terms of the a-priori bound.  A plain module: no fixtures, no pytest hooks."""
 import ctypes
 import math
