@@ -810,6 +810,30 @@ int rick_clip_attention_bwd_f32(const float *qkv, const float *g_out, float *sta
 int rick_clip_input_bwd_f32(const float *g, float *out, int N, int H, int W, int S, int P, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * DINOv2 — the ViT of DINOv2 (Oquab et al., 2023; rick_amd/dinov2.py): the final LayerNorm's class token, the feature space of
+ * FD-DINOv2 (Stein et al., 2023).  Forward only.  It runs on the CLIP section's transformer (rick_clip_layernorm_f32 with
+ * eps = 1e-6, rick_clip_attention_f32, rick_inc_conv_lin_f32 for the patch embedding and q/k/v) and adds what that lacks:
+ * rick_inc_conv_vit_f32: rick_inc_conv_lin_f32's GEMM (same operands, same descriptor checks, same tiles, exact fp32 products,
+ *   no split-K, nseg = 1) with the epilogue, in this order, v = acc + bias[col]; v = act(v); v = v * scale[col] if
+ *   scale != NULL; v = v + res[m, col] if res != NULL.  Every operation is rounded on its own (nothing is contracted into an
+ *   FMA).  act = 0 is the identity, act = 1 the exact GELU 0.5f * u * (1.f + erff(u * 0.70710678118654752f)) in that operation
+ *   order: (0.5f * u) * (1.f + erff(.)).  It is finite for every finite u; erff is exactly +-1 from |u| = 6 on, so such a u
+ *   comes back as u itself or as a zero.  scale is [Co] floats (LayerScale).  res follows rick_inc_conv_lin_f32's rules,
+ *   res == dst[0] included.  Any other act returns 22.  A row's result does not depend on the other rows.
+ * rick_vit_input_f32: rick_clip_input_f32 (the same kernel: resize rule, tap order, the affine's four correctly rounded
+ *   operations, NHWC4 output) with mean and std of the affine as arguments; with CLIP's constants the bits of
+ *   rick_clip_input_f32.  mean finite, std finite and > 0, else 22.
+ * rick_vit_tokens_f32: patches [N, T - 1, C], cls [C], pos [T, C] -> out [N, T, C]: out[n, 0, :] = cls + pos[0],
+ *   out[n, t, :] = patches[n, t - 1, :] + pos[t].  One fp32 add per element, 16-byte accesses, no LayerNorm.  C % 4 == 0,
+ *   C <= 2048, 2 <= T <= 257, N T C / 1024 (the blocks of the launch) below 2^31, every pointer 16-byte aligned; else 22.
+ * All of them: one writer per output element, fixed summation order, no atomics, no host branch on device data. */
+int rick_inc_conv_vit_f32(const float *in, const float *wpk, const float *bias, const float *scale, const float *res, int act,
+                          const rick_inc_conv *a, void *stream);
+int rick_vit_input_f32(const float *x, float *out, int N, int H, int W, int S, float mean0, float mean1, float mean2, float std0,
+                       float std1, float std2, void *stream);
+int rick_vit_tokens_f32(const float *patches, const float *cls, const float *pos, float *out, int N, int T, int C, void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * Gram — the Gram matrix of a few very long rows and its adjoint (rick_amd/cdc.py): the device side of the cross-domain
  * distance-consistency loss, which needs the cosine similarity of whole generator feature maps between batch members.
  * x is B rows (1 <= B <= 8) of n >= 1 fp32 values, row stride n, 64-bit indices.  A row is an unordered bag of values: any

@@ -247,6 +247,9 @@ SIGNATURES = {
     'rick_clip_text_tokens_f32': (c_int, [c_fp] * 4 + [c_int] * 4 + [c_fp]),
     'rick_clip_attention_causal_f32': (c_int, [c_fp, c_fp, c_int, c_int, c_int, c_int, c_fp]),
     'rick_clip_layernorm_rows_f32': (c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_f, c_fp]),
+    'rick_inc_conv_vit_f32': (c_int, [c_fp] * 5 + [c_int, ctypes.POINTER(IncConv), c_fp]),
+    'rick_vit_input_f32': (c_int, [c_fp, c_fp] + [c_int] * 4 + [c_f] * 6 + [c_fp]),
+    'rick_vit_tokens_f32': (c_int, [c_fp] * 4 + [c_int] * 3 + [c_fp]),
 }
 
 if not os.path.exists(LIB_PATH):

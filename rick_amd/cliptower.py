@@ -7,7 +7,11 @@ and issues the launches of a block:
 
 The towers differ around that: the stem that fills the residual stream, the rows the final LayerNorm reads, and whether the
 attention is causal.  What differs inside the blocks is data (the attention entry and the buffers a layer reads and writes),
-handed to ``Transformer`` as arguments.  The shared library is imported when a launch is built, not before."""
+handed to ``Transformer`` as arguments.  The shared library is imported when a launch is built, not before.
+
+DINOv2's ViT (rick_amd/dinov2.py) is a third tower on the same blocks.  What it changes inside them is data as well: the table
+of key names, the LayerNorm eps, the activation (the exact GELU), a LayerScale vector behind either branch and no projection.
+The defaults are CLIP's."""
 import copy
 import functools
 import math
@@ -33,8 +37,13 @@ def _lib():
 
 
 # ---- loading --------------------------------------------------------------------------------------------------------------
-_BLOCK_OPENAI = {'ln1': 'ln_1', 'out': 'attn.out_proj', 'ln2': 'ln_2', 'fc': 'mlp.c_fc', 'proj': 'mlp.c_proj'}
-_BLOCK_HF = {'ln1': 'layer_norm1', 'out': 'self_attn.out_proj', 'ln2': 'layer_norm2', 'fc': 'mlp.fc1', 'proj': 'mlp.fc2'}
+# A table of block key names: the modules of ln1, out, ln2, fc and proj (each with .weight and .bias); 'qkv', either the three
+# modules of q, k and v or the (weight, bias) keys of the fused projection, rows q, k, v; optionally 'ls1' and 'ls2', the keys
+# of the LayerScale vectors [Wd] behind the attention and the MLP.
+_BLOCK_OPENAI = {'ln1': 'ln_1', 'qkv': ('attn.in_proj_weight', 'attn.in_proj_bias'), 'out': 'attn.out_proj', 'ln2': 'ln_2',
+                 'fc': 'mlp.c_fc', 'proj': 'mlp.c_proj'}
+_BLOCK_HF = {'ln1': 'layer_norm1', 'qkv': ('self_attn.q_proj', 'self_attn.k_proj', 'self_attn.v_proj'), 'out': 'self_attn.out_proj',
+             'ln2': 'layer_norm2', 'fc': 'mlp.fc1', 'proj': 'mlp.fc2'}
 
 
 def shape(sd, key, who):
@@ -50,11 +59,13 @@ def layer_count(keys, prefix, who):
     return max(idx) + 1
 
 
-def blocks_from_state_dict(sd, prefix, hf, wd, who):
-    """The blocks `prefix`{i}. of width wd in the transformers (hf) or the OpenAI layout -> (their parameters as fp32 CPU
-    tensors under the layout-free names blocks.{i}.{ln1,qkv,out,ln2,fc,proj}.{w,b}, the keys of sd that were read).  The
-    transformers layout's q, k and v are concatenated into qkv, rows q, k, v."""
-    p, used, block = {}, set(), _BLOCK_HF if hf else _BLOCK_OPENAI
+def blocks_from_state_dict(sd, prefix, hf, wd, who, block=None):
+    """The blocks `prefix`{i}. of width wd under the key names of the table `block` (CLIP's of the transformers (hf) or the
+    OpenAI layout unless one is given) -> (their parameters as fp32 CPU tensors under the layout-free names
+    blocks.{i}.{ln1,qkv,out,ln2,fc,proj}.{w,b} and, where the table names them, blocks.{i}.{ls1,ls2}; the keys of sd that were
+    read).  Separate q, k and v are concatenated into qkv, rows q, k, v."""
+    p, used = {}, set()
+    block = block or (_BLOCK_HF if hf else _BLOCK_OPENAI)
 
     def take(key, shape_):
         used.add(key)
@@ -63,16 +74,19 @@ def blocks_from_state_dict(sd, prefix, hf, wd, who):
     for i in range(layer_count(sd.keys(), prefix, who)):
         src, dst = f'{prefix}{i}.', f'blocks.{i}.'
         mlp = shape(sd, f'{src}{block["fc"]}.weight', who)[0]
-        if hf:
-            parts = [take(f'{src}self_attn.{proj}_proj.{suffix}', shape_)
-                     for suffix, shape_ in (('weight', (wd, wd)), ('bias', (wd,))) for proj in 'qkv']
+        if len(block['qkv']) == 3:
+            parts = [take(f'{src}{proj}.{suffix}', shape_)
+                     for suffix, shape_ in (('weight', (wd, wd)), ('bias', (wd,))) for proj in block['qkv']]
             p[dst + 'qkv.w'], p[dst + 'qkv.b'] = torch.cat(parts[:3]).contiguous(), torch.cat(parts[3:]).contiguous()
         else:
-            p[dst + 'qkv.w'] = take(src + 'attn.in_proj_weight', (3 * wd, wd))
-            p[dst + 'qkv.b'] = take(src + 'attn.in_proj_bias', (3 * wd,))
+            p[dst + 'qkv.w'] = take(src + block['qkv'][0], (3 * wd, wd))
+            p[dst + 'qkv.b'] = take(src + block['qkv'][1], (3 * wd,))
         for name, shape_ in (('ln1', None), ('out', (wd, wd)), ('ln2', None), ('fc', (mlp, wd)), ('proj', (wd, mlp))):
             p[f'{dst}{name}.w'] = take(f'{src}{block[name]}.weight', shape_ or (wd,))
             p[f'{dst}{name}.b'] = take(f'{src}{block[name]}.bias', (shape_[0],) if shape_ else (wd,))
+        for name in ('ls1', 'ls2'):
+            if name in block:
+                p[dst + name] = take(src + block[name], (wd,))
     return p, used
 
 
@@ -110,20 +124,38 @@ def limits(p, wd, tokens, heads, noun, who):
 
 
 # ---- the blocks as a plain torch composition ------------------------------------------------------------------------------
-def torch_blocks(p, cfg, t, mask=None):
+ACTIVATIONS = ('quickgelu', 'gelu')      # u sigmoid(1.702 u) (CLIP); the exact 0.5 u (1 + erf(u / sqrt 2)) (DINOv2)
+
+
+def check_activation(act, who):
+    if act not in ACTIVATIONS:
+        raise RuntimeError(f'{who}: activation {act!r}, expected one of {ACTIVATIONS}')
+
+
+def layer_scales(p, i):
+    """(ls1, ls2) of block i, the LayerScale vectors [Wd] behind its attention and its MLP; None where p has none."""
+    return p.get(f'blocks.{i}.ls1'), p.get(f'blocks.{i}.ls2')
+
+
+def torch_blocks(p, cfg, t, mask=None, eps=EPS, act='quickgelu'):
     """The L blocks on the residual stream t [n, T, Wd], in the dtype and on the device of t and the parameters p; mask: an
-    additive [T, T] mask on the attention scores (the text tower's causal one)."""
+    additive [T, T] mask on the attention scores (the text tower's causal one); eps: of the LayerNorms; act: one of
+    ACTIVATIONS.  Where p holds blocks.{i}.ls1 / ls2 (LayerScale), the branch is multiplied by it before it joins the stream."""
+    check_activation(act, 'torch_blocks')
     wd, d, T = cfg.width, cfg.width // cfg.heads, cfg.tokens
     n = t.shape[0]
     for i in range(cfg.layers):
         b = f'blocks.{i}.'
-        h = F.layer_norm(t, (wd,), p[b + 'ln1.w'], p[b + 'ln1.b'], EPS)
+        ls1, ls2 = layer_scales(p, i)
+        h = F.layer_norm(t, (wd,), p[b + 'ln1.w'], p[b + 'ln1.b'], eps)
         q, k, v = (u.view(n, T, cfg.heads, d).transpose(1, 2) for u in F.linear(h, p[b + 'qkv.w'], p[b + 'qkv.b']).split(wd, 2))
         s = q @ k.transpose(2, 3) * (1.0 / math.sqrt(d))
         a = torch.softmax(s if mask is None else s + mask, -1) @ v
-        t = t + F.linear(a.transpose(1, 2).reshape(n, T, wd), p[b + 'out.w'], p[b + 'out.b'])
-        h = F.linear(F.layer_norm(t, (wd,), p[b + 'ln2.w'], p[b + 'ln2.b'], EPS), p[b + 'fc.w'], p[b + 'fc.b'])
-        t = t + F.linear(h * torch.sigmoid(1.702 * h), p[b + 'proj.w'], p[b + 'proj.b'])
+        a = F.linear(a.transpose(1, 2).reshape(n, T, wd), p[b + 'out.w'], p[b + 'out.b'])
+        t = t + (a if ls1 is None else a * ls1)
+        h = F.linear(F.layer_norm(t, (wd,), p[b + 'ln2.w'], p[b + 'ln2.b'], eps), p[b + 'fc.w'], p[b + 'fc.b'])
+        h = F.linear(h * torch.sigmoid(1.702 * h) if act == 'quickgelu' else F.gelu(h), p[b + 'proj.w'], p[b + 'proj.b'])
+        t = t + (h if ls2 is None else h * ls2)
     return t
 
 
@@ -171,15 +203,24 @@ def gemm(what, op, a, src, res=None, act=0):
                   act, a)
 
 
-def linear(what, op, rows, k, co, src, dst, res=None, act=0):
-    """The GEMM of a linear layer, src [rows, k] -> dst [rows, co], as the 1 x 1 convolution of `rows` one-pixel images."""
+def gemm_vit(what, op, a, src, scale=None, res=None, act=0):
+    """dst = act(src * wpk + bias) [* scale] [+ res] on rick_inc_conv_vit_f32: act 1 is the exact GELU, 0 the identity; scale
+    [Co] is a LayerScale vector."""
+    return launch(what, 'rick_inc_conv_vit_f32', src.data_ptr(), op[0].data_ptr(), op[1].data_ptr(),
+                  None if scale is None else scale.data_ptr(), None if res is None else res.data_ptr(), act, a)
+
+
+def linear(what, op, rows, k, co, src, dst, res=None, act=0, scale=None, vit=False):
+    """The GEMM of a linear layer, src [rows, k] -> dst [rows, co], as the 1 x 1 convolution of `rows` one-pixel images; vit: on
+    ``gemm_vit`` (its act, its scale) instead of ``gemm``."""
     _, _, cop, bn = op
-    return gemm(what, op, gemm_conv.descriptor(rows, 1, 1, k, (1, 1), (1, 1), (0, 0), cop, bn, [(dst.data_ptr(), co, 0, co)]), src, res, act)
+    a = gemm_conv.descriptor(rows, 1, 1, k, (1, 1), (1, 1), (0, 0), cop, bn, [(dst.data_ptr(), co, 0, co)])
+    return gemm_vit(what, op, a, src, scale, res, act) if vit else gemm(what, op, a, src, res, act)
 
 
-def layernorm(what, w, b, src, ldx, dst, rows, width):
+def layernorm(what, w, b, src, ldx, dst, rows, width, eps=EPS):
     """LayerNorm of `rows` rows of src, ldx floats apart, into the contiguous rows of dst."""
-    return launch(what, 'rick_clip_layernorm_f32', src.data_ptr(), ldx, w.data_ptr(), b.data_ptr(), dst.data_ptr(), rows, width, EPS)
+    return launch(what, 'rick_clip_layernorm_f32', src.data_ptr(), ldx, w.data_ptr(), b.data_ptr(), dst.data_ptr(), rows, width, eps)
 
 
 # ---- the blocks and the projection on the device --------------------------------------------------------------------------
@@ -196,10 +237,18 @@ class Transformer:
     res[2 i + 2], and keeps q|k|v in qkv[i].  Without pre, c_fc runs with the fused QuickGELU epilogue; with it, c_fc writes
     the pre-activation to pre[i] with the identity epilogue and rick_clip_quickgelu_f32 follows: the same bits.  A new
     object runs in place, every res `tok` and every qkv the one buffer; ``wired`` gives a view on other buffers.  The
-    launches are resolved once per n."""
+    launches are resolved once per n.
 
-    def __init__(self, p, cfg, batch, device, who, attention, tables=('pos',), stem=()):
-        self.cfg, self.batch, self.attention = cfg, batch, attention
+    What else differs between the towers is data too.  `eps` is the LayerNorms'.  `act` is one of ACTIVATIONS, and p may hold
+    LayerScale vectors blocks.{i}.{ls1,ls2}: with 'gelu' or a LayerScale the out, fc and proj GEMMs run on
+    rick_inc_conv_vit_f32, whose epilogue has the exact GELU and the per-column scale (QuickGELU is not in that epilogue: with
+    it, fc stays where it is).  Such a network has no `pre`.  `head`: without a projection p needs no 'head', nothing of the
+    projection is built, and the caller's final LayerNorm writes the output rows itself."""
+
+    def __init__(self, p, cfg, batch, device, who, attention, tables=('pos',), stem=(), eps=EPS, act='quickgelu', head=True):
+        check_activation(act, who)
+        self.cfg, self.batch, self.attention, self.eps, self.act = cfg, batch, attention, eps, act
+        self.vit = act == 'gelu' or any(v is not None for i in range(cfg.layers) for v in layer_scales(p, i))
         rows = batch * cfg.tokens
         self.vec = {k: v.to(device) for k, v in p.items() if v.dim() == 1 or k in tables}
 
@@ -208,24 +257,28 @@ class Transformer:
             return operand(pack_linear(w, p[name + '.b'], column_block(w.shape[0], rows)), device)
 
         self.gemm = [{name: packed(f'blocks.{i}.{name}') for name in ('qkv', 'out', 'fc', 'proj')} for i in range(cfg.layers)]
-        head = pack_fc_weight(p['head'])
-        check_packed(head, cfg.width, cfg.dim, who)
-        self.head, self.head_bias = head.to(device), torch.zeros(cfg.dim, device=device, dtype=torch.float32)
         buf = lambda n: torch.empty(n, device=device, dtype=torch.float32)        # noqa: E731
+        if head:
+            packed_head = pack_fc_weight(p['head'])
+            check_packed(packed_head, cfg.width, cfg.dim, who)
+            self.head, self.head_bias = packed_head.to(device), torch.zeros(cfg.dim, device=device, dtype=torch.float32)
         self.stem = [buf(n) for n in stem]
         self.tok, self.ln, self.att = (buf(rows * cfg.width) for _ in range(3))
-        self.qkv, self.hid, self.post = buf(rows * 3 * cfg.width), buf(rows * cfg.mlp), buf(batch * cfg.width)
-        self.ws = buf(fc_workspace(batch, cfg.width, cfg.dim))
+        self.qkv, self.hid = buf(rows * 3 * cfg.width), buf(rows * cfg.mlp)
+        if head:
+            self.post, self.ws = buf(batch * cfg.width), buf(fc_workspace(batch, cfg.width, cfg.dim))
         self.res, self.qkvs, self.pre, self._launches = [self.tok] * (2 * cfg.layers + 1), [self.qkv] * cfg.layers, None, {}
 
     def wired(self, res, qkv, pre=None):
         """This object on other buffers per layer (see the class): the same operands, scratch and projection, its own launches."""
+        if pre is not None and self.vit:
+            raise RuntimeError('Transformer: a kept pre-activation needs the QuickGELU kernel; there is none for GELU or LayerScale')
         other = copy.copy(self)
         other.res, other.qkvs, other.pre, other._launches = res, qkv, pre, {}
         return other
 
     def layernorm(self, what, name, src, ldx, dst, rows):
-        return layernorm(what, self.vec[name + '.w'], self.vec[name + '.b'], src, ldx, dst, rows, self.cfg.width)
+        return layernorm(what, self.vec[name + '.w'], self.vec[name + '.b'], src, ldx, dst, rows, self.cfg.width, self.eps)
 
     def launches(self, n):
         """The launches of the L blocks for n sequences, in order."""
@@ -234,17 +287,18 @@ class Transformer:
             rows, wd = n * c.tokens, c.width
             for i, op in enumerate(self.gemm):
                 (t0, t1, t2), qkv, b = self.res[2 * i:2 * i + 3], self.qkvs[i], f'blocks.{i}.'
+                ls1, ls2 = layer_scales(self.vec, i)
                 out += [self.layernorm('ln1', b + 'ln1', t0, wd, self.ln, rows),
                         linear('qkv', op['qkv'], rows, wd, 3 * wd, self.ln, qkv),
                         launch('attention', self.attention, qkv.data_ptr(), self.att.data_ptr(), n, c.tokens, c.heads, wd // c.heads),
-                        linear('out', op['out'], rows, wd, wd, self.att, t1, res=t0),
+                        linear('out', op['out'], rows, wd, wd, self.att, t1, res=t0, scale=ls1, vit=self.vit),
                         self.layernorm('ln2', b + 'ln2', t1, wd, self.ln, rows)]
                 if self.pre is None:
-                    out.append(linear('fc', op['fc'], rows, wd, c.mlp, self.ln, self.hid, act=1))
+                    out.append(linear('fc', op['fc'], rows, wd, c.mlp, self.ln, self.hid, act=1, vit=self.act == 'gelu'))
                 else:
                     out += [linear('fc', op['fc'], rows, wd, c.mlp, self.ln, self.pre[i]),              # the pre-activation, kept
                             launch('quickgelu', 'rick_clip_quickgelu_f32', self.pre[i].data_ptr(), self.hid.data_ptr(), rows * c.mlp)]
-                out.append(linear('proj', op['proj'], rows, c.mlp, wd, self.hid, t2, res=t1))
+                out.append(linear('proj', op['proj'], rows, c.mlp, wd, self.hid, t2, res=t1, scale=ls2, vit=self.vit))
             self._launches[n] = out
         return self._launches[n]
 

@@ -9,6 +9,11 @@
 // The text tower (rick_amd/cliptext.py, forward only) shares the GEMMs, the LayerNorm and the attention kernel, the last with
 // a causal mask as a compile-time flag, and adds the token-embedding lookup and a LayerNorm of rows picked by index (ln_final
 // on each prompt's EOT row).
+//
+// DINOv2's ViT (rick_amd/dinov2.py, forward only) shares the input kernel (the affine's constants are kernel arguments), the
+// GEMMs, the LayerNorm and the attention kernel, and adds the stem without ln_pre (vit_tokens_kernel).
+#include <float.h>
+
 #include "common.h"
 
 #define CL_MAXJ 8              // a row of up to 2048 columns in registers: lane l holds columns 4 l + 256 j, j < 8
@@ -33,8 +38,13 @@ __device__ __forceinline__ void cl_cubic_taps(int dst, float scale, int n_in, in
     for (int k = 0; k < 4; k++) idx[k] = min(max(i0 - 1 + k, 0), n_in - 1);   // border: clamped source indices
 }
 
+// mean and std of the affine arrive as kernel arguments: CLIP's constants from rick_clip_input_f32, the caller's from
+// rick_vit_input_f32.  The four operations are correctly rounded, so a constant gives the same bits either way.
+struct cl_affine {
+    float mean[3], std[3];
+};
 __global__ __launch_bounds__(256) void clip_input_kernel(const float *__restrict__ x, float *__restrict__ out, int N, int H, int W,
-                                                         int S, float sh, float sw) {
+                                                         int S, float sh, float sw, cl_affine k) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= (int64_t)N * S * S) return;
     const int ox = (int)(i % S), oy = (int)((i / S) % S), n = (int)(i / ((int64_t)S * S));
@@ -42,7 +52,6 @@ __global__ __launch_bounds__(256) void clip_input_kernel(const float *__restrict
     float wy[4], wx[4];
     cl_cubic_taps(oy, sh, H, iy, wy);
     cl_cubic_taps(ox, sw, W, ix, wx);
-    const float mean[3] = {0.48145466f, 0.4578275f, 0.40821073f}, std[3] = {0.26862954f, 0.26130258f, 0.27577711f};
     float r[3];
 #pragma unroll
     for (int c = 0; c < 3; c++) {
@@ -57,7 +66,7 @@ __global__ __launch_bounds__(256) void clip_input_kernel(const float *__restrict
             v = a == 0 ? wy[0] * row : fmaf(wy[a], row, v);
         }
         // (v * 0.5 + 0.5 - mean) / std: four correctly rounded fp32 operations, as torch evaluates the expression
-        r[c] = __fdiv_rn(__fsub_rn(__fadd_rn(__fmul_rn(v, 0.5f), 0.5f), mean[c]), std[c]);
+        r[c] = __fdiv_rn(__fsub_rn(__fadd_rn(__fmul_rn(v, 0.5f), 0.5f), k.mean[c]), k.std[c]);
     }
     reinterpret_cast<float4 *>(out)[i] = make_float4(r[0], r[1], r[2], 0.f);
 }
@@ -260,6 +269,21 @@ __global__ __launch_bounds__(256) void clip_text_tokens_kernel(const int *__rest
     const int c = (int)(i % C4), t = (int)(row % T);
     const int id = min(max(ids[row], 0), V - 1);
     const float4 a = reinterpret_cast<const float4 *>(table)[(int64_t)id * C4 + c];
+    const float4 d = reinterpret_cast<const float4 *>(pos)[(int64_t)t * C4 + c];
+    reinterpret_cast<float4 *>(out)[i] = make_float4(a.x + d.x, a.y + d.y, a.z + d.z, a.w + d.w);
+}
+
+// The stem of a ViT without ln_pre (DINOv2): out[n, 0, :] = cls + pos[0], out[n, t, :] = patches[n, t - 1, :] + pos[t].  The
+// element -> thread map and the one fp32 add of clip_text_tokens_kernel.
+__global__ __launch_bounds__(256) void vit_tokens_kernel(const float *__restrict__ patches, const float *__restrict__ cls,
+                                                         const float *__restrict__ pos, float *__restrict__ out, int64_t total, int T,
+                                                         int C4) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;                // over [N T][C / 4]
+    if (i >= total) return;
+    const int64_t row = i / C4, n = row / T;
+    const int c = (int)(i % C4), t = (int)(row % T);
+    const float4 a = t == 0 ? reinterpret_cast<const float4 *>(cls)[c]
+                            : reinterpret_cast<const float4 *>(patches)[(n * (T - 1) + (t - 1)) * C4 + c];
     const float4 d = reinterpret_cast<const float4 *>(pos)[(int64_t)t * C4 + c];
     reinterpret_cast<float4 *>(out)[i] = make_float4(a.x + d.x, a.y + d.y, a.z + d.z, a.w + d.w);
 }
@@ -662,13 +686,26 @@ static bool cl_aligned16(const void *a, const void *b = nullptr, const void *c =
     return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)d) % 16) == 0;
 }
 
-extern "C" int rick_clip_input_f32(const float *x, float *out, int N, int H, int W, int S, void *stream) {
+static int cl_input_entry(const float *x, float *out, int N, int H, int W, int S, const cl_affine &k, void *stream) {
     if (!x || !out || N < 0 || H <= 0 || W <= 0 || S <= 0 || !cl_aligned16(out)) return RICK_EINVAL;
     if ((int64_t)H * W > 0x7fffffff / 4 || (int64_t)N * S * S > ((int64_t)1 << 36)) return RICK_EINVAL;
     if (N == 0) return 0;
     hipLaunchKernelGGL(clip_input_kernel, dim3((unsigned)cdiv64((int64_t)N * S * S, 256)), dim3(256), 0, (hipStream_t)stream, x, out,
-                       N, H, W, S, (float)H / (float)S, (float)W / (float)S);
+                       N, H, W, S, (float)H / (float)S, (float)W / (float)S, k);
     RICK_LAUNCH_STATUS();
+}
+
+extern "C" int rick_clip_input_f32(const float *x, float *out, int N, int H, int W, int S, void *stream) {
+    return cl_input_entry(x, out, N, H, W, S, cl_affine{{0.48145466f, 0.4578275f, 0.40821073f}, {0.26862954f, 0.26130258f, 0.27577711f}},
+                          stream);
+}
+
+extern "C" int rick_vit_input_f32(const float *x, float *out, int N, int H, int W, int S, float mean0, float mean1, float mean2,
+                                  float std0, float std1, float std2, void *stream) {
+    const cl_affine k{{mean0, mean1, mean2}, {std0, std1, std2}};
+    for (int c = 0; c < 3; c++)
+        if (!(fabsf(k.mean[c]) <= FLT_MAX) || !(k.std[c] > 0.f && k.std[c] <= FLT_MAX)) return RICK_EINVAL;     // finite, std > 0
+    return cl_input_entry(x, out, N, H, W, S, k, stream);
 }
 
 extern "C" int rick_clip_layernorm_f32(const float *in, int64_t ldx, const float *w, const float *b, float *out, int R, int C,
@@ -719,6 +756,19 @@ extern "C" int rick_clip_text_tokens_f32(const int32_t *ids, const float *table,
     if (cdiv64(total, 256) > 0x7fffffff) return RICK_EINVAL;                  // the grid's x extent
     hipLaunchKernelGGL(clip_text_tokens_kernel, dim3((unsigned)cdiv64(total, 256)), dim3(256), 0, (hipStream_t)stream, ids, table, pos,
                        out, total, T, V, C / 4);
+    RICK_LAUNCH_STATUS();
+}
+
+extern "C" int rick_vit_tokens_f32(const float *patches, const float *cls, const float *pos, float *out, int N, int T, int C,
+                                   void *stream) {
+    if (!patches || !cls || !pos || !out || N < 0 || T < 2 || T > CL_MAXT || C <= 0 || (C & 3) || C > CL_MAXC ||
+        !cl_aligned16(patches, cls, pos, out))
+        return RICK_EINVAL;
+    if (N == 0) return 0;
+    const int64_t total = (int64_t)N * T * (C / 4);
+    if (cdiv64(total, 256) > 0x7fffffff) return RICK_EINVAL;                  // the grid's x extent
+    hipLaunchKernelGGL(vit_tokens_kernel, dim3((unsigned)cdiv64(total, 256)), dim3(256), 0, (hipStream_t)stream, patches, cls, pos, out,
+                       total, T, C / 4);
     RICK_LAUNCH_STATUS();
 }
 

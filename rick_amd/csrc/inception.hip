@@ -72,6 +72,13 @@ __device__ __forceinline__ float4 inc_ld_b(const float *wpk, int k0, int idx, in
 __device__ __forceinline__ float inc_quickgelu(float u) {
     return __fmul_rn(u, __fdiv_rn(1.f, __fadd_rn(1.f, expf(-__fmul_rn(1.702f, u)))));
 }
+// LIN >= 3 is the ViT epilogue (rick_inc_conv_vit_f32): out = act(acc + bias) [* scale[col]] [+ res], act the identity (LIN = 3)
+// or the exact GELU (LIN = 4), scale (LayerScale, the `mask` argument) one float per column, res as above.  Every operation
+// is rounded on its own.  The exact GELU: 0.5f * u * (1.f + erff(u * 0.70710678118654752f)), in that order.  erff saturates
+// to +-1 from |x| = 4 on, so u >= 6 comes back as u and u <= -6 as -0.
+__device__ __forceinline__ float inc_gelu(float u) {
+    return __fmul_rn(__fmul_rn(0.5f, u), __fadd_rn(1.f, erff(__fmul_rn(u, 0.70710678118654752f))));
+}
 template <int NT, bool BWD = false, int LIN = 0>
 __global__ __launch_bounds__(256) void inc_conv_kernel(const float *__restrict__ in, const float *__restrict__ wpk,
                                                        const float *__restrict__ bias, rick_inc_conv a,
@@ -168,6 +175,27 @@ __global__ __launch_bounds__(256) void inc_conv_kernel(const float *__restrict__
                     if (add) v += add[o];
                     if (mask) v = mask[o] > 0.f ? v : 0.f;
                     a.dst[0][o] = v;
+                }
+            continue;
+        }
+        if constexpr (LIN >= 3) {
+            float *dst = a.dst[0] + a.c0[0] + col;
+            // the in-place residual is read through the destination pointer: `add` is __restrict__
+            const float *res = add == a.dst[0] ? a.dst[0] : add;
+            if (res) res += a.c0[0] + col;
+            const float b = bias[col], sc = mask ? mask[col] : 1.f;
+#pragma unroll
+            for (int i = 0; i < 2; i++)
+#pragma unroll
+                for (int e = 0; e < 16; e++) {
+                    const int m = m0 + wm * 64 + 32 * i + (e & 3) + 8 * (e >> 2) + 4 * h;
+                    if (m >= M) continue;
+                    const int64_t o = (int64_t)m * a.ldc[0];
+                    float v = __fadd_rn(acc[i][j][e], b);
+                    if (LIN == 4) v = inc_gelu(v);
+                    if (mask) v = __fmul_rn(v, sc);
+                    if (res) v = __fadd_rn(v, res[o]);
+                    dst[o] = v;
                 }
             continue;
         }
@@ -412,10 +440,8 @@ extern "C" int rick_inc_conv_bwd_f32(const float *gout, const float *wt, const f
     RICK_LAUNCH_STATUS();
 }
 
-extern "C" int rick_inc_conv_lin_f32(const float *in, const float *wpk, const float *bias, const float *res, int act,
-                                     const rick_inc_conv *a, void *stream) {
-    if (!in || !wpk || !bias || !a || (act != 0 && act != 1)) return RICK_EINVAL;
-    const rick_inc_conv g = *a;
+// what the one-destination epilogues (rick_inc_conv_lin_f32, rick_inc_conv_vit_f32) accept of a descriptor and its operands
+static int inc_lin_domain(const float *in, const float *wpk, const rick_inc_conv &g) {
     if (g.N < 0 || g.IH <= 0 || g.IW <= 0 || g.Ci <= 0 || (g.Ci & 3) || g.KH <= 0 || g.KW <= 0 || g.SH <= 0 || g.SW <= 0 ||
         g.PH < 0 || g.PW < 0 || g.Co <= 0 || g.nseg != 1 || (g.bn != 64 && g.bn != 128) || g.Cop % g.bn || g.Cop < g.Co)
         return RICK_EINVAL;
@@ -425,10 +451,20 @@ extern "C" int rick_inc_conv_lin_f32(const float *in, const float *wpk, const fl
     if (g.seg_start[0] != 0 || g.seg_start[1] < g.Co || g.seg_start[2] < g.Co || g.seg_start[3] < g.Co || !g.dst[0] ||
         g.c0[0] < 0 || g.c0[0] + g.Co > g.ldc[0])
         return RICK_EINVAL;
+    if ((int64_t)g.N * g.OH * g.OW > 0x7fffffff || (int64_t)g.N * g.IH * g.IW * g.Ci > ((int64_t)1 << 40)) return RICK_EINVAL;
+    return 0;
+}
+static dim3 inc_lin_grid(const rick_inc_conv &g) {
+    return dim3((unsigned)cdiv64((int64_t)g.N * g.OH * g.OW, IC_BM), (unsigned)(g.Cop / g.bn));
+}
+
+extern "C" int rick_inc_conv_lin_f32(const float *in, const float *wpk, const float *bias, const float *res, int act,
+                                     const rick_inc_conv *a, void *stream) {
+    if (!in || !wpk || !bias || !a || (act != 0 && act != 1)) return RICK_EINVAL;
+    const rick_inc_conv g = *a;
+    if (inc_lin_domain(in, wpk, g)) return RICK_EINVAL;
     if (g.N == 0) return 0;
-    const int64_t M = (int64_t)g.N * g.OH * g.OW;
-    if (M > 0x7fffffff || (int64_t)g.N * g.IH * g.IW * g.Ci > ((int64_t)1 << 40)) return RICK_EINVAL;
-    const dim3 grid((unsigned)cdiv64(M, IC_BM), (unsigned)(g.Cop / g.bn));
+    const dim3 grid = inc_lin_grid(g);
     hipStream_t st = (hipStream_t)stream;
     if (g.bn == 128 && act)
         hipLaunchKernelGGL((inc_conv_kernel<2, false, 2>), grid, dim3(256), 0, st, in, wpk, bias, g, nullptr, res);
@@ -438,6 +474,25 @@ extern "C" int rick_inc_conv_lin_f32(const float *in, const float *wpk, const fl
         hipLaunchKernelGGL((inc_conv_kernel<1, false, 2>), grid, dim3(256), 0, st, in, wpk, bias, g, nullptr, res);
     else
         hipLaunchKernelGGL((inc_conv_kernel<1, false, 1>), grid, dim3(256), 0, st, in, wpk, bias, g, nullptr, res);
+    RICK_LAUNCH_STATUS();
+}
+
+extern "C" int rick_inc_conv_vit_f32(const float *in, const float *wpk, const float *bias, const float *scale, const float *res,
+                                     int act, const rick_inc_conv *a, void *stream) {
+    if (!in || !wpk || !bias || !a || (act != 0 && act != 1)) return RICK_EINVAL;
+    const rick_inc_conv g = *a;
+    if (inc_lin_domain(in, wpk, g)) return RICK_EINVAL;
+    if (g.N == 0) return 0;
+    const dim3 grid = inc_lin_grid(g);
+    hipStream_t st = (hipStream_t)stream;
+    if (g.bn == 128 && act)
+        hipLaunchKernelGGL((inc_conv_kernel<2, false, 4>), grid, dim3(256), 0, st, in, wpk, bias, g, scale, res);
+    else if (g.bn == 128)
+        hipLaunchKernelGGL((inc_conv_kernel<2, false, 3>), grid, dim3(256), 0, st, in, wpk, bias, g, scale, res);
+    else if (act)
+        hipLaunchKernelGGL((inc_conv_kernel<1, false, 4>), grid, dim3(256), 0, st, in, wpk, bias, g, scale, res);
+    else
+        hipLaunchKernelGGL((inc_conv_kernel<1, false, 3>), grid, dim3(256), 0, st, in, wpk, bias, g, scale, res);
     RICK_LAUNCH_STATUS();
 }
 
