@@ -652,6 +652,11 @@ int rick_is_accum_f64(const float *p, const double *s, const double *h, double *
  *   weights w [C] (C <= 1024) -> part[s][i][j] (fp64) = sum over the positions [s pps, (s + 1) pps) of slice s and all
  *   channels of w_c (fa_ic ia_i - fb_jc ib_j)^2, for s < ceil(HW / pps).  Summation order depends on (position, channel)
  *   only: d(x, x) = 0 and D(A, B) = D(B, A)^T exactly, and a pair's value does not depend on the other images of the call.
+ * rick_lpips_paired_f32: one tap of n pairs, image i of fa against image i of fb only.  Image i of fa is at fa + i sa HW C with
+ *   its inverse norms at ia + i sa HW (sa, sb >= 1: strides in images; with sa = sb = 2, fb = fa + HW C and ib = ia + HW one set of
+ *   2n interleaved images serves as both operands) -> part[s][i] (fp64), the layout rick_lpips_reduce_f32 reads with na = n,
+ *   nb = 1.  Every value is bit-identical to part[s][i][i] of rick_lpips_pair_f32 for the same two images: the same fp32 chain
+ *   inside each 256-element stage, the same fp64 sum of stages.  Work and partials are proportional to n.  pps * C <= 8192.
  * rick_lpips_reduce_f32: part = the nlayers taps' partials one after the other ([nslices[l]][na][nb] each) -> out [na, nb]
  *   fp32 = sum over taps in order of (sum over slices in order) / hw[l], in fp64.
  * The backward pass of the paired distance (rick_amd/lpips.py: LPIPS.loss), first order, with respect to the image:
@@ -679,12 +684,28 @@ int rick_lpips_maxpool2_f32(const float *in, float *out, int N, int IH, int IW, 
 int rick_lpips_invnorm_f32(const float *in, float *out, int64_t P, int C, void *stream);
 int rick_lpips_pair_f32(const float *fa, const float *ia, int na, const float *fb, const float *ib, int nb, const float *w,
                         int HW, int C, int pps, double *part, void *stream);
+int rick_lpips_paired_f32(const float *fa, const float *ia, int sa, const float *fb, const float *ib, int sb, int n, const float *w,
+                          int HW, int C, int pps, double *part, void *stream);
 int rick_lpips_reduce_f32(const double *part, float *out, int na, int nb, const rick_lpips_layers *d, void *stream);
 int rick_lpips_tap_bwd_f32(const float *a, const float *ia, const float *t, const float *it, int n, int nt, const float *w,
                            const float *go, int HW, int C, int relu, float *g, void *stream);
 int rick_lpips_maxpool2_bwd_f32(const float *act, const float *add, const float *gpool, float *out, int N, int IH, int IW, int C,
                                 void *stream);
 int rick_lpips_input_bwd_f32(const float *g, float *out, int N, int H, int W, void *stream);
+
+/* ---------------------------------------------------------------------------------------
+ * PPL — the latent path points of the perceptual path length (rick_amd/ppl.py; Karras et al., StyleGAN / StyleGAN2).
+ * rick_ppl_latents_f32: a, b [B, L] fp32, t [B] -> out [2B, L]: row 2i is the path point at t[i], row 2i + 1 the point at
+ *   t[i] + eps (1 <= L <= 1024, eps finite and > 0).
+ *   mode 0 (W space): a + (b - a) t, both rows from the same fp32 d = b - a.
+ *   mode 1 (Z space): slerp.  an = a / |a|, bn = b / |b|, d = clamp(sum an bn, -1, 1), p = t acos(d), c = normalize(bn - d an),
+ *   out = normalize(an cos p + c sin p); normalize divides by max(norm, 1e-12), so a == b yields an.
+ *   One wave per pair; between the fp32 loads and stores the arithmetic is fp64 (per-lane FMA chains over elements
+ *   lane + 64 j, j ascending, then the fixed 32 ... 1 xor butterfly), so each output is the fp32 rounding of a value exact to
+ *   ~1e-15.  No atomics, run-to-run identical, capture-safe; a pair's two rows depend on that pair alone.
+ *   RICK_EINVAL for a null pointer, B < 0, L outside [1, 1024], eps not finite or <= 0, mode outside {0, 1}. */
+int rick_ppl_latents_f32(const float *a, const float *b, const float *t, double eps, float *out, int B, int L, int mode,
+                         void *stream);
 
 /* ---------------------------------------------------------------------------------------
  * VGG16 fc2 — the features behind the reference's improved precision / recall (rick_amd/vgg.py;

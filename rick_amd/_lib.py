@@ -196,10 +196,12 @@ SIGNATURES = {
     'rick_lpips_maxpool2_f32': (c_int, [c_fp, c_fp, c_int, c_int, c_int, c_int, c_fp]),
     'rick_lpips_invnorm_f32': (c_int, [c_fp, c_fp, c_i64, c_int, c_fp]),
     'rick_lpips_pair_f32': (c_int, [c_fp, c_fp, c_int, c_fp, c_fp, c_int, c_fp, c_int, c_int, c_int, c_fp, c_fp]),
+    'rick_lpips_paired_f32': (c_int, [c_fp, c_fp, c_int, c_fp, c_fp, c_int, c_int, c_fp, c_int, c_int, c_int, c_fp, c_fp]),
     'rick_lpips_reduce_f32': (c_int, [c_fp, c_fp, c_int, c_int, ctypes.POINTER(LpipsLayers), c_fp]),
     'rick_lpips_tap_bwd_f32': (c_int, [c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_fp, c_fp, c_int, c_int, c_int, c_fp, c_fp]),
     'rick_lpips_maxpool2_bwd_f32': (c_int, [c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, c_fp]),
     'rick_lpips_input_bwd_f32': (c_int, [c_fp, c_fp, c_int, c_int, c_int, c_fp]),
+    'rick_ppl_latents_f32': (c_int, [c_fp, c_fp, c_fp, ctypes.c_double, c_fp, c_int, c_int, c_int, c_fp]),
     'rick_vgg_input_f32': (c_int, [c_fp, c_fp, c_int, c_int, c_int, c_fp]),
     'rick_fc_packed_floats': (c_i64, [c_int, c_int]),
     'rick_fc_workspace_floats': (c_i64, [c_int, c_int, c_int]),

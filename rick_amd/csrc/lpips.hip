@@ -155,6 +155,77 @@ __global__ __launch_bounds__(256) void lp_pair_kernel(const float *__restrict__ 
     if (i < na && j < nb) part[((int64_t)slice * na + i) * nb + j] = acc;
 }
 
+// ---- paired partials of one tap: image i of fa against image i of fb only --------------------------------------------------------
+// part[slice][i] = what lp_pair_kernel writes to part[slice][i][i], bit for bit, for n pairs instead of n^2.  The pair kernel's
+// value is fixed by three orders: inside a stage of LP_KC elements one fp32 chain s = fma(w_c, (a ia - b ib)^2, s) in element
+// order from 0, the stage sums added to an fp64 accumulator in stage order, the slices added by lp_reduce_kernel.  Block =
+// (slice, pair): all 256 threads stream the slice of both images once and leave q = (a ia - b ib)^2 in LDS (the same three fp32
+// roundings as lp_stage + the pair loop: two products, one difference, one square — fp contraction is off in this file), then
+// thread k < 32 runs stage k's chain over its LDS row (row stride LP_LD: the 32 rows' float4 reads fall on distinct banks), and
+// thread 0 adds the stage sums in order.  A slice holds at most LP_PSTAGES stages (pps * C <= 8192, checked by the entry).
+#define LP_PSTAGES 32
+
+// (a sa - b sb)^2 as four scalar-lane instructions, each one correctly rounded fp32 operation like the compiler's own v_mul_f32 /
+// v_sub_f32 in lp_stage and lp_pair_kernel; written out because the compiler pairs the four channels of a float4 into
+// v_pk_mul_f32 / v_pk_add_f32 here, and the build keeps this file's distance kernels scalar (tools/check_isa.py)
+__device__ __forceinline__ float lp_sqdiff(float a, float sa, float b, float sb) {
+    float u, v, d, q;
+    asm("v_mul_f32 %0, %1, %2" : "=v"(u) : "v"(a), "v"(sa));
+    asm("v_mul_f32 %0, %1, %2" : "=v"(v) : "v"(b), "v"(sb));
+    asm("v_sub_f32 %0, %1, %2" : "=v"(d) : "v"(u), "v"(v));
+    asm("v_mul_f32 %0, %1, %2" : "=v"(q) : "v"(d), "v"(d));
+    return q;
+}
+
+__global__ __launch_bounds__(256) void lp_paired_kernel(const float *__restrict__ fa, const float *__restrict__ ia, int64_t sa,
+                                                        const float *__restrict__ fb, const float *__restrict__ ib, int64_t sb,
+                                                        int n, const float *__restrict__ w, int HW, int C, int pps, int nsl,
+                                                        double *__restrict__ part) {
+    __shared__ __attribute__((aligned(16))) float Qs[LP_PSTAGES * LP_LD];
+    __shared__ __attribute__((aligned(16))) float Ws[LP_MAXC];
+    __shared__ float Ss[LP_PSTAGES];
+    const int t = threadIdx.x;
+    const int slice = (int)(blockIdx.x % (unsigned)nsl);
+    const int64_t i = blockIdx.x / (unsigned)nsl;
+    const int pos0 = slice * pps, npos = min(pps, HW - pos0);
+    const int L = npos * C;                                            // <= LP_PSTAGES * LP_KC
+    const float *a = fa + (i * sa * HW + pos0) * C, *b = fb + (i * sb * HW + pos0) * C;
+    const float *na = ia + i * sa * HW + pos0, *nb = ib + i * sb * HW + pos0;
+    for (int c = t; c < C; c += 256) Ws[c] = w[c];
+    for (int e = 4 * t; e < L; e += 1024) {
+        const int p = e / C;
+        const float s1 = na[p], s2 = nb[p];
+        const float4 x = *reinterpret_cast<const float4 *>(a + e), y = *reinterpret_cast<const float4 *>(b + e);
+        const float4 q = make_float4(lp_sqdiff(x.x, s1, y.x, s2), lp_sqdiff(x.y, s1, y.y, s2), lp_sqdiff(x.z, s1, y.z, s2),
+                                     lp_sqdiff(x.w, s1, y.w, s2));
+        *reinterpret_cast<float4 *>(Qs + (e / LP_KC) * LP_LD + (e % LP_KC)) = q;
+    }
+    __syncthreads();
+    const int nst = (L + LP_KC - 1) / LP_KC;
+    if (t < nst) {
+        const int e0 = t * LP_KC, kc = min(LP_KC, L - e0);
+        const float *q = Qs + t * LP_LD;
+        int c = e0 % C;
+        float s = 0.f;
+        for (int k = 0; k < kc; k += 4) {
+            const float4 qv = *reinterpret_cast<const float4 *>(q + k), wv = *reinterpret_cast<const float4 *>(Ws + c);
+            s = fmaf(wv.x, qv.x, s);
+            s = fmaf(wv.y, qv.y, s);
+            s = fmaf(wv.z, qv.z, s);
+            s = fmaf(wv.w, qv.w, s);
+            c += 4;
+            if (c == C) c = 0;
+        }
+        Ss[t] = s;
+    }
+    __syncthreads();
+    if (t == 0) {
+        double acc = 0.0;
+        for (int k = 0; k < nst; k++) acc += (double)Ss[k];
+        part[(int64_t)slice * n + i] = acc;
+    }
+}
+
 // ---- second stage: out[i][j] = sum over taps (in order) of (sum over slices, in order) / HW_l --------------------------------
 __global__ __launch_bounds__(256) void lp_reduce_kernel(const double *__restrict__ part, float *__restrict__ out, int na, int nb,
                                                         rick_lpips_layers d) {
@@ -308,6 +379,20 @@ extern "C" int rick_lpips_pair_f32(const float *fa, const float *ia, int na, con
     if (nsl > 0x7fffffff || cdiv64(na, LP_TILE) > 65535 || cdiv64(nb, LP_TILE) > 65535) return RICK_EINVAL;
     const dim3 grid((unsigned)nsl, (unsigned)cdiv64(na, LP_TILE), (unsigned)cdiv64(nb, LP_TILE));
     hipLaunchKernelGGL(lp_pair_kernel, grid, dim3(256), 0, (hipStream_t)stream, fa, ia, na, fb, ib, nb, w, HW, C, pps, part);
+    RICK_LAUNCH_STATUS();
+}
+
+extern "C" int rick_lpips_paired_f32(const float *fa, const float *ia, int sa, const float *fb, const float *ib, int sb, int n,
+                                     const float *w, int HW, int C, int pps, double *part, void *stream) {
+    if (!fa || !ia || !fb || !ib || !w || !part || sa < 1 || sb < 1 || n < 0 || HW <= 0 || C <= 0 || (C & 3) || C > LP_MAXC || pps <= 0)
+        return RICK_EINVAL;
+    if ((((uintptr_t)fa | (uintptr_t)fb) % 16) || ((uintptr_t)part % 8)) return RICK_EINVAL;
+    if ((int64_t)(pps < HW ? pps : HW) * C > LP_PSTAGES * LP_KC) return RICK_EINVAL;     // a slice must fit the LDS rows
+    if (n == 0) return 0;
+    const int64_t nsl = cdiv64(HW, pps);
+    if (nsl * n > 0x7fffffff) return RICK_EINVAL;
+    hipLaunchKernelGGL(lp_paired_kernel, dim3((unsigned)(nsl * n)), dim3(256), 0, (hipStream_t)stream, fa, ia, (int64_t)sa, fb, ib,
+                       (int64_t)sb, n, w, HW, C, pps, (int)nsl, part);
     RICK_LAUNCH_STATUS();
 }
 

@@ -479,3 +479,9 @@ class Evaluator:
         return intra_lpips(self.generator, centers, lpips, n_samples=n_samples, n_sample_store=self.n_sample_store,
                            cluster_size=cluster_size, fid_sample_size=self.sample_size, latent=self.latent, size=size,
                            latents=latents, rng=rng)[0]
+
+    def compute_ppl(self, lpips, **kw):
+        """The perceptual path length of the generator (``rick_amd.ppl.perceptual_path_length``, whose keywords ``kw`` are)
+        -> the filtered mean."""
+        from .ppl import perceptual_path_length
+        return perceptual_path_length(self.generator, lpips, **kw)[0]

@@ -19,6 +19,8 @@ torchvision's ``vgg16().features``:
 An image's taps do not depend on the image it is compared with, so ``features`` runs the trunk once per image and keeps the
 five taps (NHWC) and their per-position inverse norms; ``distances`` then forms every pair of two feature sets with
 rick_lpips_pair_f32 in the direct form ``sum_c w_c (a_c ia - b_c ib)^2`` (never the Gram form, which cancels on near pairs).
+``paired`` forms only image i against image i (rick_lpips_paired_f32: the same sums in the same order, so the same bits as
+the diagonal of ``distances``, for n pairs of work instead of n^2); ``net(x, y)`` and the no-grad ``net.loss`` run on it.
 
 CUDA fp32 inputs run the kernels of rick_amd/csrc/lpips.hip and the Inception convolution rick_inc_conv_f32 (f32-input MFMA,
 no split-K: an image's taps are bit-identical whatever batch it is computed in).  The workspace (input, two ping-pong
@@ -265,11 +267,9 @@ class _LpipsLoss(torch.autograd.Function):
         ws = net._grad_workspace()
         with torch.cuda.device(net.device):
             f = ws.forward(x)
-            # n x n pairs for n values, as __call__ does: the pair kernel's 25 x 25 at 256^2 is about 2 ms next to the
-            # trunk's ~30 ms, and one launch per tap is cheaper than n launches of one pair each
-            d = net.distances(f, target)
+            d = net.paired(f, target) if target.n == f.n and f.n > 1 else net.distances(f, target)[:, 0].contiguous()
         ctx.net, ctx.target, ctx.f, ctx.version = net, target, f, ws.version
-        return torch.diagonal(d).contiguous() if target.n == f.n and f.n > 1 else d[:, 0].contiguous()
+        return d
 
     @staticmethod
     def backward(ctx, go):
@@ -396,6 +396,59 @@ class LPIPS:
                       'rick_lpips_reduce_f32')
         return out
 
+    @torch.no_grad()
+    def paired(self, fa, fb=None):
+        """[n] fp32: LPIPS between image i of fa and image i of fb (LpipsFeatures of n images each).  With ``fb=None`` the
+        pairs are the rows (2i, 2i + 1) of fa, which must hold an even number of images: one feature set serves as both
+        operands.  On the device this is rick_lpips_paired_f32 (n pairs of work and partials, not n^2) and every value is
+        bit-identical to the diagonal of ``distances``."""
+        if fb is None:
+            if fa.n % 2:
+                raise RuntimeError(f'LPIPS.paired: {fa.n} images cannot be paired as rows (2i, 2i + 1)')
+            n, stride = fa.n // 2, 2
+        else:
+            if fa.size != fb.size or fa.device != fb.device or fa.n != fb.n:
+                raise RuntimeError(f'LPIPS.paired: {fa.n} images of {fa.size} on {fa.device} against {fb.n} of {fb.size} on '
+                                   f'{fb.device}')
+            n, stride = fa.n, 1
+        if fa.device.type == 'cpu':
+            if fb is None:
+                fa, fb = (LpipsFeatures([t[k::2] for t in fa.taps], [t[k::2] for t in fa.inorm]) for k in (0, 1))
+            out = torch.zeros(n, dtype=torch.float64)
+            for s in range(5):
+                a = (fa.taps[s] * fa.inorm[s].view(fa.taps[s].shape[:3])[..., None]).flatten(1, 2)   # [n, HW, C]
+                b = (fb.taps[s] * fb.inorm[s].view(fb.taps[s].shape[:3])[..., None]).flatten(1, 2)
+                out += (((a - b) ** 2) * self.lins[s]).sum(2).mean(1).double()
+            return out.float()
+        lib = self._lib()
+        hws = [t.shape[1] * t.shape[2] for t in fa.taps]
+        nsl = [-(-hw // _positions_per_slice(c)) for hw, c in zip(hws, CHANNELS)]
+        out = torch.empty(n, device=fa.device, dtype=torch.float32)
+        if n == 0:
+            return out
+        part = torch.empty(sum(nsl) * n, device=fa.device, dtype=torch.float64)
+        d = lib.LpipsLayers()
+        d.nlayers = 5
+        with torch.cuda.device(fa.device):
+            stream, off = lib.stream_ptr(), 0
+            for s in range(5):
+                sets = (fa,) if fb is None else (fa, fb)
+                if not all(f.taps[s].is_contiguous() and f.inorm[s].is_contiguous() for f in sets):
+                    raise RuntimeError('LPIPS.paired: feature tensors must be contiguous')
+                ta, ia = fa.taps[s].data_ptr(), fa.inorm[s].data_ptr()
+                if fb is None:                       # image 2i + 1 lies one image behind image 2i
+                    tb, ib = ta + 4 * hws[s] * CHANNELS[s], ia + 4 * hws[s]
+                else:
+                    tb, ib = fb.taps[s].data_ptr(), fb.inorm[s].data_ptr()
+                lib.check(lib.lib.rick_lpips_paired_f32(ta, ia, stride, tb, ib, stride, n, self._plan.lins[s].data_ptr(), hws[s],
+                                                        CHANNELS[s], _positions_per_slice(CHANNELS[s]), part[off:].data_ptr(),
+                                                        stream), 'rick_lpips_paired_f32')
+                d.nslices[s], d.hw[s] = nsl[s], hws[s]
+                off += nsl[s] * n
+            lib.check(lib.lib.rick_lpips_reduce_f32(part.data_ptr(), out.data_ptr(), n, 1, ctypes.byref(d), stream),
+                      'rick_lpips_reduce_f32')
+        return out
+
     @staticmethod
     def _lib():
         from . import _lib
@@ -436,8 +489,8 @@ class LPIPS:
                 val = val + ((nx - ny) ** 2 * self.lins[s].view(1, -1, 1, 1)).sum(1).mean((1, 2))
             return val
         if not needs_grad:
-            d = self.distances(self.features(x, quantize), target)
-            return torch.diagonal(d).contiguous() if target.n == N and N > 1 else d[:, 0].contiguous()
+            f = self.features(x, quantize)
+            return self.paired(f, target) if target.n == N and N > 1 else self.distances(f, target)[:, 0].contiguous()
         if N * H * W > self._plan.pixels:
             raise ValueError(f'LPIPS.loss: {N} images of {H} x {W} exceed the workspace planned for {self.batch} x '
                              f'{self.size}^2')
@@ -475,5 +528,5 @@ class LPIPS:
             hi = min(N, lo + step)
             a = self.features(x[lo:hi], quantize, out=fx)
             b = self.features(y[lo:hi], quantize, out=fy)
-            out[lo:hi] = torch.diagonal(self.distances(a, b))
+            out[lo:hi] = self.paired(a, b)
         return out

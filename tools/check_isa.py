@@ -25,7 +25,7 @@ PACKED = re.compile(r'^\s*(v_pk_fma_f32|v_pk_mul_f32|v_pk_add_f32)\b')
 CROSS = re.compile(r'^\s*(ds_bpermute_b32|ds_permute_b32|ds_swizzle_b32|v_permlane\w*|v_readlane_b32|v_writelane_b32|v_\w+_dpp)\b')
 # kernels whose cross-lane sums were wrong in the packed form, or share its pattern (LDS-broadcast operand x FMA chain -> wave sum)
 NO_PACKING = {'modulation.hip': ['modbank_fwd_kernel'], 'linear.hip': ['linear_fwd_kernel', 'linear_dgrad_kernel', 'linear_wgrad_kernel'],
-              'lpips.hip': ['lp_invnorm_kernel', 'lp_pair_kernel'], 'gram.hip': ['gram_kernel', 'xgram_kernel'],
+              'lpips.hip': ['lp_invnorm_kernel', 'lp_pair_kernel', 'lp_paired_kernel'], 'ppl.hip': ['ppl_latents_kernel'], 'gram.hip': ['gram_kernel', 'xgram_kernel'],
               'kml.hip': ['kml_grad_kernel'], 'svd.hip': ['svd_grad_kernel'], 'patchd.hip': ['patch_head_fwd_kernel'],
               'clip.hip': ['clip_layernorm_kernel', 'clip_tokens_kernel', 'clip_attention_kernel', 'clip_layernorm_bwd_kernel',
                            'clip_tokens_bwd_kernel', 'clip_attention_bwd_q_kernel', 'clip_attention_bwd_kv_kernel', 'clip_layernorm_rows_kernel']}
@@ -33,7 +33,7 @@ NO_PACKING = {'modulation.hip': ['modbank_fwd_kernel'], 'linear.hip': ['linear_f
 
 PER_FILE = {'linear.hip': ['-fno-slp-vectorize'], 'lpips.hip': ['-fno-slp-vectorize'], 'gram.hip': ['-fno-slp-vectorize'],
             'kml.hip': ['-fno-slp-vectorize'], 'svd.hip': ['-fno-slp-vectorize'], 'patchd.hip': ['-fno-slp-vectorize'],
-            'clip.hip': ['-fno-slp-vectorize']}      # (rick_amd/csrc/Makefile: target-specific CXXFLAGS)
+            'clip.hip': ['-fno-slp-vectorize'], 'ppl.hip': ['-fno-slp-vectorize']}      # (rick_amd/csrc/Makefile: target-specific CXXFLAGS)
 
 
 def device_asm(src):
